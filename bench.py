@@ -18,7 +18,7 @@ No PyTorch anywhere (north_star): device memory and streams come from ggs.hip
 communicators, their id from a file rendezvous on the node.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S]
-                    [--config 512|1024|1024x8]
+                    [--config 512|1024|1024x8] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` outside a launcher starts N rank processes itself (before anything
@@ -32,11 +32,28 @@ strong scaling).  Synthetic data: genomes from the population.py:20-46
 distributions (4 populations resident in HBM, cycled step to step), target
 U[0,1], mask U[0.405,1].
 
-Timing: W untimed steps, then passes of exactly K steps, each bracketed by a
-barrier + device synchronize on both sides; passes repeat until >= --min-time
-seconds were measured (the driver's --steps 20 is ~3 ms, inside launch/clock
-jitter); the reported time is the median pass, after taking the max over ranks
-pass by pass.
+A plain run does only what the headline needs: set-up, clock ramp, warm-up, the
+timed steps, the result line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, the configuration and the runtimes).  `--full` adds
+everything else the line can carry, each from runs of its own: the CPU baseline
+(numpy oracle on the host cores), `value_one_stream`, `value_with_readback`,
+the unplanned device-API rate (`plan_excluded`), the per-kernel HIP-event pass
+with the HBM / VALU roofline figures against the committed profiles, the AABB
+pair count and the PCIe-inclusive host-API rate.  `--extras 0` and
+`--no-cpu-baseline` narrow a `--full` run as before.
+
+`--dump-outputs DIR` writes what the last timed step delivered as float32 .npy
+files: `DIR/fitness.npy`, the B fitness scalars of this rank's candidates, and,
+when the step gathers, `DIR/fitness_gathered.npy`, the world x B scalars every
+rank receives (rank 0 writes; inputs are seeded, so two builds given the same
+arguments can be compared output for output).
+
+Timing: an untimed clock ramp (--ramp-ms), W untimed steps, then one pass of
+exactly K steps bracketed by a barrier + device synchronize on both sides:
+--steps is the number of timed steps, and `ms_per_step` that pass's time over K
+(max over ranks).  --steps 20 is ~3 ms, inside launch/clock jitter: give more
+steps, or --min-time S to repeat the K-step pass until S seconds were measured
+and report the median pass (`timing.passes` says how many).
 """
 from __future__ import annotations
 
@@ -506,10 +523,18 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: CPU baseline, one-stream / "
+                         "readback / unplanned rates, per-kernel pass and rooflines, host-API rate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (fitness scalars) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="512")
-    ap.add_argument("--min-time", type=float, default=0.5,
-                    help="repeat the K-step timed pass until this many seconds were measured")
+    ap.add_argument("--min-time", type=float, default=None,
+                    help="repeat the K-step timed pass until this many seconds were measured and report "
+                         "the median pass (default: the headline times exactly one pass of --steps "
+                         "steps; the --full passes beside it measure 0.5 s each)")
     ap.add_argument("--ramp-ms", type=float, default=300.0,
                     help="untimed steps before the warm-up, until the clocks have ramped")
     ap.add_argument("--streams", type=int, default=STREAMS,
@@ -518,7 +543,7 @@ def parse_args(argv=None):
                     help="candidates per GPU per batch (0: the config's; other values explore batch size "
                          "and are not the BASELINE workload)")
     ap.add_argument("--extras", type=int, default=1,
-                    help="0: headline pass only (profiling runs)")
+                    help="with --full, 0: headline pass only (profiling runs)")
     ap.add_argument("--watchdog-init-s", type=float, default=300.0,
                     help="deadline of the communicator set-up and the first barrier")
     ap.add_argument("--watchdog-floor-s", type=float, default=30.0,
@@ -556,13 +581,14 @@ def run(args, world, rank, local_rank, distributed):
         POP = args.pop if args.pop > 0 else pop_cfg
         global_batch = POP * world
     headline = args.config == "512" and POP == 128
+    extras_on = bool(args.full and args.extras)
 
     rng = np.random.default_rng(1234)
     tgt_h = rng.uniform(0, 1, (H, W, 3)).astype(np.float32)
     mask_h = rng.uniform(0.405, 1.0, (H, W)).astype(np.float32)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and headline and args.extras:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and headline and extras_on:
         cpu = cpu_baseline(tgt_h, mask_h)
 
     # HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default); the
@@ -680,10 +706,10 @@ def run(args, world, rank, local_rank, distributed):
         wd.collective(0)
         return comms[0].allgather_host(v.astype(np.float32)).astype(np.float64).max(0)
 
-    def timed(ns):
+    def timed(ns, min_time):
         """W untimed steps, then passes of exactly K steps, each bracketed by
-        barrier + synchronize, until --min-time seconds were measured (the same
-        number of passes on every rank).  Returns (median pass seconds after the
+        barrier + synchronize, until min_time seconds were measured (the same
+        number of passes on every rank; 0: one pass).  Returns (median pass seconds after the
         max over ranks per pass, passes, host enqueue seconds of the first pass)."""
         arm(f"warm-up ({args.warmup} steps, {ns} stream(s))", args.warmup)
         for i in range(args.warmup):
@@ -700,26 +726,35 @@ def run(args, world, rank, local_rank, distributed):
             return time.perf_counter() - t0, host_s
 
         first, host_s = one_pass()
-        reps = int(max_over_ranks([min(1000, max(1, math.ceil(args.min_time / max(first, 1e-9))))])[0])
+        reps = int(max_over_ranks([min(1000, max(1, math.ceil(min_time / max(first, 1e-9))))])[0])
         passes = [first] + [one_pass()[0] for _ in range(reps - 1)]
         per_pass = max_over_ranks(passes)
         return float(np.median(per_pass)), len(passes), host_s
 
     barrier()                  # first collective's one-time set-up before the ramp, not after it
     ramp(args.ramp_ms, args.streams)
-    elapsed, passes, host_s = timed(args.streams)          # the headline
+    # the headline: --steps timed steps, no more unless --min-time asks for repeats
+    elapsed, passes, host_s = timed(args.streams, args.min_time or 0.0)
+    min_time = 0.5 if args.min_time is None else args.min_time      # of each --full pass below
     shard_ok = True
     if comms is not None and GATHER != "none":             # the gather delivered this rank's shard
         j = (args.steps - 1) % RING
         shard_ok = np.array_equal(gathered[j].to_host()[rank * POP:(rank + 1) * POP], outs[j].to_host())
+    if args.dump_outputs and rank == 0:                    # before the extra passes reuse the ring
+        j = (args.steps - 1) % RING
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "fitness.npy"), outs[j].to_host().astype(np.float32))
+        if comms is not None and GATHER != "none":
+            np.save(os.path.join(args.dump_outputs, "fitness_gathered.npy"),
+                    gathered[j].to_host().astype(np.float32))
 
     extras = {}
     kern = {}
-    if args.extras:
+    if extras_on:
         # dependent batches (a GA generation needs the previous one's fitness): one stream
         if args.streams > 1:
             ramp(args.ramp_ms / 3, 1)
-            elapsed1, passes1, _ = timed(1)
+            elapsed1, passes1, _ = timed(1, min_time)
         else:
             elapsed1, passes1 = elapsed, passes
         extras["value_one_stream"] = round(world * POP * args.steps / elapsed1, 1)
@@ -727,10 +762,10 @@ def run(args, world, rank, local_rank, distributed):
         # + the D2H of the B fitness scalars each step (fitness.py:42 .cpu()) and a host sync
         ramp(args.ramp_ms / 3, 1)
         host_out = np.empty(POP, np.float32)
-        arm("readback passes", extra_s=args.min_time)
+        arm("readback passes", extra_s=min_time)
         t0 = time.perf_counter()
         n_rb = 0
-        while time.perf_counter() - t0 < args.min_time:
+        while time.perf_counter() - t0 < min_time:
             for i in range(args.steps):
                 step(i, 1, gather=False)
                 hip.memcpy_d2h_async(host_out, outs[i % RING].ptr, POP * 4, streams[0])
@@ -745,11 +780,11 @@ def run(args, world, rank, local_rank, distributed):
         # (ggs_fitness_device) rebuilds it on every call: its one-stream rate, and the
         # plan build alone (host-timed around a synchronised ggs_plan_create).
         ramp(args.ramp_ms / 3, 1)
-        arm("unplanned device-API passes", extra_s=2 * args.min_time)
+        arm("unplanned device-API passes", extra_s=2 * min_time)
 
         def loop_rate(one):      # seconds per step of one stream, no gathers, same loop shape
             t0, n = time.perf_counter(), 0
-            while time.perf_counter() - t0 < args.min_time:
+            while time.perf_counter() - t0 < min_time:
                 for i in range(args.steps):
                     one(i)
                 streams[0].synchronize()
@@ -794,18 +829,20 @@ def run(args, world, rank, local_rank, distributed):
         assert shard_ok, "fitness all-gather returned a different shard"
 
     # algorithmic work of this workload (AABB pairs from the product's own prep)
-    pairs = 0
-    for p in pops_h:
-        pre = ggs.preprocess(ggs.encode(p), H, W, K_SIGMA)
-        pairs += int(((pre["x1"].astype(np.int64) - pre["x0"] + 1) *
-                      (pre["y1"].astype(np.int64) - pre["y0"] + 1)).sum())
-    pairs_per_cand = pairs / (N_POPS * POP)
+    pairs_per_cand = None
+    if args.full:
+        pairs = 0
+        for p in pops_h:
+            pre = ggs.preprocess(ggs.encode(p), H, W, K_SIGMA)
+            pairs += int(((pre["x1"].astype(np.int64) - pre["x0"] + 1) *
+                          (pre["y1"].astype(np.int64) - pre["y0"] + 1)).sum())
+        pairs_per_cand = pairs / (N_POPS * POP)
 
     # PCIe-inclusive rate of the host API (numpy genomes in, fitness scalars out:
     # target/mask content check, pinned staging, 3 launches, D2H) — the path a
     # caller handing over host buffers gets; reported beside, never the value
     host_api = None
-    if world == 1 and args.extras:
+    if world == 1 and extras_on:
         ggs.fitness(pops_h[0], tgt_h, H, W, K_SIGMA, weight_mask=mask_h, device=local_rank)
         n_h, t_h = 0, time.perf_counter()
         while time.perf_counter() - t_h < 0.5:
@@ -894,6 +931,7 @@ def run(args, world, rank, local_rank, distributed):
                                 "gets, value_with_readback adds the per-step D2H of the fitness scalars"),
             "n_gpus": world,
             "steps": args.steps,
+            "full": bool(args.full),
             "warmup": args.warmup,
             "ms_per_step": round(ms_step, 4),
             "higher_is_better": True,
@@ -914,7 +952,7 @@ def run(args, world, rank, local_rank, distributed):
             "timing": {"passes": passes, "statistic": "median pass of K steps (max over ranks per pass)",
                        "measured_s": round(elapsed * passes, 3)},
             "gsplat_pixels_per_s": round(value * N_SPLATS * H * W / 1e9, 2),
-            "aabb_pairs_per_s": round(value * pairs_per_cand, 1),
+            "aabb_pairs_per_s": None if pairs_per_cand is None else round(value * pairs_per_cand, 1),
             "roofline": roof,
             "valu": valu if kern else None,
             "streams": args.streams,

@@ -70,7 +70,8 @@ def _run_world(tmp_path, argv, world=2, slow_rank=1, corrupt=False, stall=None):
     return [p.exitcode for p in procs], logs, out0
 
 
-FAST = ["--steps", "3", "--warmup", "2", "--min-time", "0.02", "--ramp-ms", "1", "--no-cpu-baseline"]
+# --full: the one-stream / readback / unplanned passes, the per-kernel pass and the rooflines
+FAST = ["--steps", "3", "--warmup", "2", "--min-time", "0.02", "--ramp-ms", "1", "--full", "--no-cpu-baseline"]
 
 
 def test_bench_world2_orchestration(tmp_path):
@@ -94,6 +95,61 @@ def test_bench_world2_orchestration(tmp_path):
     pe = line["plan_excluded"]
     assert pe["device_api_unplanned_value"] > 0 and pe["plan_build_ms"] >= 0
     assert not (tmp_path / "stdout1.txt").read_text().strip()               # rank 1 prints nothing
+
+
+def _stand_in_fitness(rank, step):
+    """What tests/_fakes.py's evaluation returns for the population of that step."""
+    import bench
+    G = bench.synthetic_population(128, 256, 10_000 * rank + step % bench.N_POPS)
+    return G.reshape(128, -1).sum(1, dtype=np.float32)
+
+
+def test_plain_run_measures_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline (metric, value, unit,
+    higher_is_better, dtype, ms_per_step) and none of the figures that take runs of
+    their own; --dump-outputs writes the last timed step's fitness scalars (step
+    K - 1: population (K - 1) % 4), identically from run to run."""
+    dumps = []
+    for name in ("a", "b"):
+        run_dir = tmp_path / name
+        run_dir.mkdir()
+        codes, logs, out0 = _run_world(run_dir, ["--gpus", "1", "--dump-outputs", str(run_dir / "out"),
+                                                 "--steps", "3", "--warmup", "2", "--ramp-ms", "1"],
+                                       world=1, slow_rank=None)
+        assert codes == [0], logs
+        assert len(out0) == 1
+        dumps.append(np.load(run_dir / "out" / "fitness.npy"))
+        assert sorted(os.listdir(run_dir / "out")) == ["fitness.npy"]
+    line = json.loads(out0[0])
+    assert line["full"] is False and line["steps"] == 3 and line["warmup"] == 2
+    assert line["timing"]["passes"] == 1           # --steps is the number of timed steps
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "candidate renders/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "fp32" and "512x512" in line["metric"]
+    # value is candidates per timed-step second (ms_per_step is rounded to 1e-4 ms)
+    rel = 5e-5 / line["ms_per_step"] + 1e-6
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 / 128 - 1) <= rel
+    for k in ("value_one_stream", "value_with_readback", "plan_excluded"):
+        assert k not in line, k
+    for k in ("roofline", "valu", "cpu_baseline", "host_api_renders_per_s", "aabb_pairs_per_s",
+              "kernels_ms_rocprof", "kernel_timing_note"):
+        assert line[k] is None, k
+    assert line["kernels_ms_per_launch"] == {}
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (128,)
+    np.testing.assert_array_equal(dumps[0], _stand_in_fitness(0, 2))
+    np.testing.assert_array_equal(dumps[0], dumps[1])
+
+
+def test_full_run_dumps_the_headline_step_and_the_gathered_scalars(tmp_path):
+    """--full reuses the ring of output slots in its extra passes: the dump is
+    still the headline's last step, and at world 2 rank 0 also writes the
+    world x B scalars the gather delivered."""
+    out = tmp_path / "out"
+    codes, logs, out0 = _run_world(tmp_path, ["--gpus", "2", "--dump-outputs", str(out)] + FAST)
+    assert codes == [0, 0], logs
+    assert json.loads(out0[0])["full"] is True
+    np.testing.assert_array_equal(np.load(out / "fitness.npy"), _stand_in_fitness(0, 2))
+    np.testing.assert_array_equal(np.load(out / "fitness_gathered.npy"),
+                                  np.concatenate([_stand_in_fitness(0, 2), _stand_in_fitness(1, 2)]))
 
 
 @pytest.mark.parametrize("world", [4, 8])

@@ -7,10 +7,11 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out; export TMPDIR=/tmp
 R=${1:-r04}
+OUT=${GGS_OUT_DIR:-out}; mkdir -p "$OUT"   # logs of this run
 for c in 1024 1024x8; do
-  timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline > gpurun_out/${R}_bench_$c.log 2>&1 || exit $?
-  grep '^{' gpurun_out/${R}_bench_$c.log | tail -1 > gpurun_out/${R}_bench_$c.json
-  python3 -c "import json; d=json.load(open('gpurun_out/${R}_bench_$c.json')); print('$c', d['value'], d['ms_per_step'], d['kernels_ms_per_launch'])"
+  timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 3 --full --no-cpu-baseline > "$OUT/${R}_bench_$c.log" 2>&1 || exit $?
+  grep '^{' "$OUT/${R}_bench_$c.log" | tail -1 > "$OUT/${R}_bench_$c.json"
+  python3 -c "import json; d=json.load(open('$OUT/${R}_bench_$c.json')); print('$c', d['value'], d['ms_per_step'], d['kernels_ms_per_launch'])"
 done
 bash tools/profile_configs.sh $R > gpurun_out/${R}_profile_configs.log 2>&1 || { tail -5 gpurun_out/${R}_profile_configs.log; exit 1; }
 tail -12 gpurun_out/${R}_profile_configs.log

@@ -4,7 +4,7 @@
 set -e
 cd $GRAFT_REPO_ROOT
 ALT=${ALT:-libggs_new}
-BENCH_ARGS=${BENCH_ARGS:-"--no-cpu-baseline --steps 200"}
+BENCH_ARGS=${BENCH_ARGS:-"--full --no-cpu-baseline --steps 200"}
 P=genetic-gaussian-splats_amd
 for L in $ALT; do
   echo "$L: $(timeout -k 10 300 python tools/probe/bitcmp.py $P/libggs.so $P/$L.so 2>&1 | tail -1)" >> gpurun_out/ab_bitcmp.log

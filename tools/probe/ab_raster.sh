@@ -5,7 +5,7 @@
 cd $GRAFT_REPO_ROOT
 P=genetic-gaussian-splats_amd
 LIBS=${LIBS:-"libggs"}
-BENCH_ARGS=${BENCH_ARGS:-"--no-cpu-baseline"}
+BENCH_ARGS=${BENCH_ARGS:-"--full --no-cpu-baseline"}
 for i in 1 2; do
   for L in $LIBS; do
     GGS_LIB=$PWD/$P/$L.so timeout -k 10 200 python bench.py $BENCH_ARGS > gpurun_out/ab_$L.$i.log 2>&1 || { tail -5 gpurun_out/ab_$L.$i.log; exit 1; }

@@ -16,6 +16,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out; export TMPDIR=/tmp
 TAG=${1:?tag}; PART=${2:?A or B}
+OUT=${GGS_OUT_DIR:-out}; mkdir -p "$OUT"   # logs of this run
 ok() { local rc=$1; echo "[$2] rc=$rc"; [ "$rc" -eq 0 ] || exit "$rc"; }
 show() { python3 - "$1" <<'PY'
 import json, sys
@@ -34,9 +35,9 @@ if [ "$PART" = A ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread -p no:cacheprovider \
       > gpurun_out/${TAG}_pytest_gpu.log 2>&1; ok $? pytest_gpu
   tail -2 gpurun_out/${TAG}_pytest_gpu.log
-  timeout -k 10 300 python bench.py > gpurun_out/${TAG}_bench.log 2>&1; ok $? bench
-  grep '^{' gpurun_out/${TAG}_bench.log | tail -1 > gpurun_out/${TAG}_bench_line.json
-  cut -c1-400 gpurun_out/${TAG}_bench_line.json; echo
+  timeout -k 10 300 python bench.py --full > "$OUT/${TAG}_bench.log" 2>&1; ok $? bench
+  grep '^{' "$OUT/${TAG}_bench.log" | tail -1 > "$OUT/${TAG}_bench_line.json"
+  cut -c1-400 "$OUT/${TAG}_bench_line.json"; echo
   bash tools/profile.sh $TAG > gpurun_out/${TAG}_profile.log 2>&1; ok $? profile_$TAG
   show gpurun_out/prof_$TAG/summary.json
   bash tools/profile_configs.sh $TAG > gpurun_out/${TAG}_profile_configs.log 2>&1; ok $? profile_configs
