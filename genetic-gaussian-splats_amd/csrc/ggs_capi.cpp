@@ -229,10 +229,12 @@ void prof_drain_locked() {
 }
 
 // raster (MODE 1) + finalize of B candidates: one launch when `fuse` (and allowed).
+// group > 0: plan / wpartials are a plan set's and candidate b is scored against
+// plan b / group.
 int raster_fitness(hipStream_t st, int simds, const SplatRec* recs, const int4* bnds, int B, int N, int H, int W,
                    const float4* plan, float* partials, const float* wpartials, int mode, const int* order,
                    DevBuf& ctr, float* out, bool fuse, const unsigned char* dirty = nullptr,
-                   const float* clean = nullptr) {
+                   const float* clean = nullptr, int group = 0) {
     const float bg[3] = {1.f, 1.f, 1.f};  // fitness renders with the default background (fitness.py:15)
     int nTX;
     const int nTiles = raster_tiles(H, W, &nTX);
@@ -251,16 +253,16 @@ int raster_fitness(hipStream_t st, int simds, const SplatRec* recs, const int4* 
         ff.mode = mode;
         ProfScope ps(st, 1);
         GGS_HIP(launch_raster(st, 1, recs, bnds, B, N, H, W, bg, nullptr, plan, partials, order, dirty, clean,
-                              nullptr, &ff, simds));
+                              nullptr, &ff, simds, group));
         return GGS_OK;
     }
     {
         ProfScope ps(st, 1);
         GGS_HIP(launch_raster(st, 1, recs, bnds, B, N, H, W, bg, nullptr, plan, partials, order, dirty, clean,
-                              nullptr, nullptr, simds));
+                              nullptr, nullptr, simds, group));
     }
     ProfScope ps(st, 2);
-    GGS_HIP(launch_finalize(st, partials, wpartials, B, nTiles, mode, H, W, out));
+    GGS_HIP(launch_finalize(st, partials, wpartials, B, nTiles, mode, H, W, out, nullptr, group));
     return GGS_OK;
 }
 
@@ -421,7 +423,7 @@ int check_dims(int64_t B, int32_t N, int32_t C, int32_t H, int32_t W) {
 // ---- the device pipelines (ctx locked, device set) ----------------------------------
 int run_fitness_planned(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C,
                         const float4* plan, const float* wpartials, int mode, int H, int W, float k,
-                        float* d_out);
+                        float* d_out, int group = 0);
 
 // plan_key: identifies (target contents, mask contents, mode, beta, H, W) when
 // the caller knows them to be unchanged since a previous call with the same key
@@ -450,10 +452,11 @@ int run_fitness(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N,
                                (const float*)w->wpartials.p, mode, H, W, k, d_out);
 }
 
-// prep -> raster -> finalize against a ready target plan.
+// prep -> raster -> finalize against a ready target plan (group > 0: a plan set,
+// candidate b against plan b / group).
 int run_fitness_planned(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C,
                         const float4* plan, const float* wpartials, int mode, int H, int W, float k,
-                        float* d_out) {
+                        float* d_out, int group) {
     if (B == 0) return GGS_OK;
     Workspace* w = workspace_for(c, st);
     int nTX;
@@ -469,7 +472,8 @@ int run_fitness_planned(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B
         GGS_HIP(launch_prep(st, true, d_gen, B * N, C, H, W, k, recs, (int4*)w->bnds.p, nullptr, nullptr, nullptr));
     }
     return raster_fitness(st, c->simds, recs, (const int4*)w->bnds.p, (int)B, N, H, W, plan, (float*)w->partials.p,
-                          wpartials, mode, (const int*)w->order.p, w->fctr, d_out, fitness_api_fold());
+                          wpartials, mode, (const int*)w->order.p, w->fctr, d_out, fitness_api_fold(), nullptr,
+                          nullptr, group);
 }
 
 int run_render(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C, int H, int W,
@@ -624,6 +628,12 @@ struct TargetPlan {
     int H = 0, W = 0, mode = 0;
     DevBuf plan, wpartials;
 };
+// K plans plan_bytes apart and K weight blocks plan_wsum_bytes apart (launch_plan_set)
+struct PlanSet {
+    DevCtx* c = nullptr;
+    int H = 0, W = 0, mode = 0, K = 0;
+    DevBuf plan, wpartials;
+};
 }  // namespace
 }  // namespace ggs
 extern "C" {
@@ -681,6 +691,72 @@ void ggs_plan_destroy(void* plan) {
         std::lock_guard<std::mutex> lk(p->c->mu);
         DeviceGuard dg(p->c->dev);
         (void)hipDeviceSynchronize();    // streams that may still read the plan
+        if (p->plan.p) (void)hipFree(p->plan.p);
+        if (p->wpartials.p) (void)hipFree(p->wpartials.p);
+    }
+    delete p;
+}
+
+// ---- plan sets: K target plans of one (H, W, mode, beta) ------------------------
+int ggs_planset_create(int32_t device, void* stream, const float* d_targets_khw3, const float* d_masks_khw,
+                       int32_t mode, float boost_beta, int32_t H, int32_t W, int32_t K, void** planset) {
+    if (!planset || !d_targets_khw3) return fail(GGS_EINVAL, "null argument");
+    if (K < 1) return fail(GGS_EINVAL, "K=%d plans: must be >= 1", K);
+    if (mode < GGS_FIT_NONE || mode > GGS_FIT_BOOST) return fail(GGS_EINVAL, "bad fitness mode %d", mode);
+    if (mode != GGS_FIT_NONE && !d_masks_khw) return fail(GGS_EINVAL, "mode %d needs the weight masks", mode);
+    // (the set's strips are numbered through in 32 bits: K * tiles * 4 < 2^31)
+    int rc = check_dims(K, 1, 9, H, W);
+    if (rc) return rc;
+    DevCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    auto p = std::make_unique<PlanSet>();
+    p->c = c;
+    p->H = H;
+    p->W = W;
+    p->mode = mode;
+    p->K = K;
+    const hipStream_t st = (hipStream_t)stream;
+    auto bail = [&](int code) {
+        if (p->plan.p) (void)hipFree(p->plan.p);
+        if (p->wpartials.p) (void)hipFree(p->wpartials.p);
+        return code;
+    };
+    if ((rc = ensure(p->plan, (size_t)K * plan_bytes(H, W), st)) ||
+        (rc = ensure(p->wpartials, (size_t)K * plan_wsum_bytes(H, W), st)))
+        return bail(rc);
+    if (launch_plan_set(st, d_targets_khw3, d_masks_khw, mode, boost_beta, H, W, K, (float4*)p->plan.p,
+                        (float*)p->wpartials.p) != hipSuccess)
+        return bail(fail(GGS_EHIP, "plan launch failed"));
+    *planset = p.release();
+    return GGS_OK;
+}
+
+int ggs_fitness_device_planset(void* planset, void* stream, const float* d_genomes_axes, int64_t B, int32_t N,
+                               int32_t C, int32_t group, float k_sigma, float* d_out_B) {
+    if (group < 1) return fail(GGS_EINVAL, "group=%d must be >= 1", group);
+    if (B % group != 0) return fail(GGS_EINVAL, "B=%lld is not a multiple of group=%d", (long long)B, group);
+    if (!planset) return fail(GGS_EINVAL, "null plan set");
+    PlanSet* p = (PlanSet*)planset;
+    int rc = check_dims(B, N, C, p->H, p->W);
+    if (rc) return rc;
+    if (B / group > p->K)
+        return fail(GGS_EINVAL, "B / group = %lld plans wanted, the set holds %d", (long long)(B / group), p->K);
+    if (!d_out_B || (!d_genomes_axes && B > 0 && N > 0)) return fail(GGS_EINVAL, "null pointer");
+    std::lock_guard<std::mutex> lk(p->c->mu);
+    DeviceGuard dg(p->c->dev);
+    return run_fitness_planned(p->c, (hipStream_t)stream, d_genomes_axes, B, N, C, (const float4*)p->plan.p,
+                               (const float*)p->wpartials.p, p->mode, p->H, p->W, k_sigma, d_out_B, group);
+}
+
+void ggs_planset_destroy(void* planset) {
+    if (!planset) return;
+    PlanSet* p = (PlanSet*)planset;
+    {
+        std::lock_guard<std::mutex> lk(p->c->mu);
+        DeviceGuard dg(p->c->dev);
+        (void)hipDeviceSynchronize();    // streams that may still read the plans
         if (p->plan.p) (void)hipFree(p->plan.p);
         if (p->wpartials.p) (void)hipFree(p->wpartials.p);
     }
@@ -1506,13 +1582,19 @@ struct GaIslands {
         best_upd, curves, seeds, mig;
     DevBuf recs, bnds, partials, plan, wpart, order, fctr;
     int64_t n_curves = 0, curves_cap = 0;
+    // a target per island (ggs_ga_islands_create_targets): target [K][H][W][3], mask
+    // [K][H][W], plan / wpart a plan set of K; island k's candidates are scored
+    // against plan k, and a migration re-scores the immigrants (mig_gen [K][m][N][9],
+    // their genomes staged compactly; mig_fits [K][m])
+    bool multi = false;
+    DevBuf mig_gen, mig_fits;
 };
 
 void gi_free(GaIslands* s) {
     for (DevBuf* b : {&s->pop[0], &s->pop[1], &s->fits[0], &s->fits[1], &s->off[0], &s->off[1], &s->elite[0],
                       &s->elite[1], &s->off_fits, &s->src, &s->target, &s->mask, &s->best_ind, &s->best_fit,
                       &s->best_src, &s->best_upd, &s->curves, &s->seeds, &s->mig, &s->recs, &s->bnds,
-                      &s->partials, &s->plan, &s->wpart, &s->order, &s->fctr})
+                      &s->partials, &s->plan, &s->wpart, &s->order, &s->fctr, &s->mig_gen, &s->mig_fits})
         if (b->p) (void)hipFree(b->p);
     if (s->st) (void)hipStreamDestroy(s->st);
 }
@@ -1568,9 +1650,32 @@ int gi_flush(GaIslands* s) {
     s->cur = nxt;
     s->n_curves += 1;
     s->pending = false;
-    if (gi_migrates(s, s->pending_gen))
+    if (gi_migrates(s, s->pending_gen) && !s->multi)
         GGS_HIP(launch_ga_migrate(s->st, s->K, (float*)s->pop[nxt].p, (float*)s->fits[nxt].p, s->P, s->N,
                                   s->n_migrants, s->cfg.elite_k, (int*)s->mig.p, (int*)s->elite[nxt].p));
+    else if (gi_migrates(s, s->pending_gen)) {
+        // A target per island: an immigrant's fitness was measured against its source
+        // island's target, so the genomes move first, the K * m immigrants are scored
+        // against their new island's plan (one prep + one grouped raster, group m; the
+        // generation's records and partials are free by now), and only then are the
+        // fitness rows installed and the elites re-ranked.
+        const int m = s->n_migrants, Bm = s->K * m;
+        const ggs_ga_config& c = s->cfg;
+        GGS_HIP(launch_ga_migrate_copy(s->st, s->K, (float*)s->pop[nxt].p, (const float*)s->fits[nxt].p, s->P, s->N,
+                                       m, (int*)s->mig.p, (float*)s->mig_gen.p));
+        {
+            ProfScope ps(s->st, 0);
+            GGS_HIP(launch_prep(s->st, true, (const float*)s->mig_gen.p, (int64_t)Bm * s->N, 9, c.H, c.W, c.k_sigma,
+                                (SplatRec*)s->recs.p, (int4*)s->bnds.p, nullptr, nullptr, nullptr));
+        }
+        if ((rc = raster_fitness(s->st, s->c->simds, (const SplatRec*)s->recs.p, (const int4*)s->bnds.p, Bm, s->N,
+                                 c.H, c.W, (const float4*)s->plan.p, (float*)s->partials.p, (const float*)s->wpart.p,
+                                 c.fitness_mode, (const int*)s->order.p, s->fctr, (float*)s->mig_fits.p, true,
+                                 nullptr, nullptr, m)))
+            return rc;
+        GGS_HIP(launch_ga_migrate_install(s->st, s->K, (float*)s->fits[nxt].p, s->P, m, c.elite_k,
+                                          (const int*)s->mig.p, (const float*)s->mig_fits.p, (int*)s->elite[nxt].p));
+    }
     return GGS_OK;
 }
 
@@ -1613,7 +1718,7 @@ int gi_generation(GaIslands* s, int gen, int total) {
     if (B > 0 && (rc = raster_fitness(s->st, s->c->simds, (const SplatRec*)s->recs.p, (const int4*)s->bnds.p, B, N,
                                       c.H, c.W, (const float4*)s->plan.p, (float*)s->partials.p,
                                       (const float*)s->wpart.p, c.fitness_mode, (const int*)s->order.p, s->fctr,
-                                      (float*)s->off_fits.p, true)))
+                                      (float*)s->off_fits.p, true, nullptr, nullptr, s->multi ? s->Pe : 0)))
         return rc;
     return GGS_OK;
 }
@@ -1638,13 +1743,10 @@ int gi_check(const ggs_ga_config* cfg, const ggs_ga_islands* isl, const float* t
     return check_dims((int64_t)isl->n_islands * cfg->pop_size, cfg->n_splats, 9, cfg->H, cfg->W);
 }
 
-}  // namespace
-}  // namespace ggs
-
-extern "C" {
-
-int ggs_ga_islands_create(int32_t device, const ggs_ga_config* cfg, const ggs_ga_islands* isl,
-                          const float* target_hw3, const float* mask_hw, const float* init_pops, void** handle) {
+// ggs_ga_islands_create (multi false: target_hw3 [H][W][3], mask_hw [H][W] shared by
+// the islands) and ggs_ga_islands_create_targets (multi: [K][H][W][3], [K][H][W]).
+int gi_create(int32_t device, const ggs_ga_config* cfg, const ggs_ga_islands* isl, const float* target_hw3,
+              const float* mask_hw, const float* init_pops, void** handle, bool multi) {
     int rc = gi_check(cfg, isl, target_hw3, mask_hw, init_pops, handle);   // before any device call
     if (rc) return rc;
     const ggs_ga_config& c = *cfg;
@@ -1658,8 +1760,13 @@ int ggs_ga_islands_create(int32_t device, const ggs_ga_config* cfg, const ggs_ga
     s->Pe = P - (c.elite_k < 1 ? 1 : c.elite_k);
     s->migrate_every = isl->migrate_every;
     s->n_migrants = isl->n_migrants;
-    const size_t KP = (size_t)K * P, B = (size_t)K * s->Pe;
-    const size_t pb = sizeof(float) * 9 * KP * N, hw = (size_t)c.H * c.W;
+    s->multi = multi;
+    const size_t nplans = multi ? (size_t)K : 1;
+    const size_t KP = (size_t)K * P;
+    // the raster batch: the generation's K * Pe offspring, or a migration's K * m immigrants
+    const size_t Bm = multi && K >= 2 && s->migrate_every > 0 ? (size_t)K * s->n_migrants : 0;
+    const size_t B = std::max((size_t)K * s->Pe, Bm);
+    const size_t pb = sizeof(float) * 9 * KP * N, hw = nplans * (size_t)c.H * c.W;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard dg(ctx->dev);
     // error returns: sync what was enqueued (the caller's arrays may be freed on return), free everything
@@ -1689,12 +1796,16 @@ int ggs_ga_islands_create(int32_t device, const ggs_ga_config* cfg, const ggs_ga
     if ((rc = ensure(s->best_src, sizeof(int) * K, s->st))) return bail(rc);
     if ((rc = ensure(s->best_upd, sizeof(int) * K, s->st))) return bail(rc);
     if ((rc = ensure(s->seeds, sizeof(uint64_t) * K, s->st))) return bail(rc);
+    if (Bm && ((rc = ensure(s->mig_gen, std::max<size_t>(sizeof(float) * 9 * Bm * N, 4), s->st)) ||
+               (rc = ensure(s->mig_fits, sizeof(float) * Bm, s->st))))
+        return bail(rc);
     int nTX;
     const size_t slots = 4 * (size_t)raster_tiles(c.H, c.W, &nTX);
     if ((rc = ensure(s->recs, sizeof(SplatRec) * std::max<size_t>(B * N, 1), s->st)) ||
         (rc = ensure(s->bnds, sizeof(int4) * std::max<size_t>(B * N, 1), s->st)) ||
         (rc = ensure(s->partials, sizeof(float) * slots * std::max<size_t>(B, 1), s->st)) ||
-        (rc = ensure(s->plan, plan_bytes(c.H, c.W), s->st)) || (rc = ensure(s->wpart, plan_wsum_bytes(c.H, c.W), s->st)) ||
+        (rc = ensure(s->plan, nplans * plan_bytes(c.H, c.W), s->st)) ||
+        (rc = ensure(s->wpart, nplans * plan_wsum_bytes(c.H, c.W), s->st)) ||
         (rc = ensure(s->order, sizeof(int) * (size_t)raster_order_len(c.H, c.W), s->st)))
         return bail(rc);
     std::vector<int> order(raster_order_len(c.H, c.W));
@@ -1705,12 +1816,18 @@ int ggs_ga_islands_create(int32_t device, const ggs_ga_config* cfg, const ggs_ga
         hipMemcpyAsync(s->seeds.p, isl->seeds, sizeof(uint64_t) * K, hipMemcpyHostToDevice, s->st) ||
         hipMemcpyAsync(s->order.p, order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice, s->st))
         return bail(fail(GGS_EHIP, "upload failed"));
-    if (launch_plan(s->st, (const float*)s->target.p, mask_hw ? (const float*)s->mask.p : nullptr, c.fitness_mode,
-                    c.boost_beta, c.H, c.W, (float4*)s->plan.p, (float*)s->wpart.p) != hipSuccess)
+    if (launch_plan_set(s->st, (const float*)s->target.p, mask_hw ? (const float*)s->mask.p : nullptr,
+                        c.fitness_mode, c.boost_beta, c.H, c.W, (int)nplans, (float4*)s->plan.p,
+                        (float*)s->wpart.p) != hipSuccess)
         return bail(fail(GGS_EHIP, "plan launch failed"));
-    if ((rc = run_fitness(ctx, s->st, (const float*)s->pop[0].p, (int64_t)KP, N, 9, (const float*)s->target.p,
-                          mask_hw ? (const float*)s->mask.p : nullptr, c.fitness_mode, c.boost_beta,
-                          c.H, c.W, c.k_sigma, (float*)s->fits[0].p, s->plan_id)))
+    if (multi) {    // the initial [K][P] population, island k's rows against plan k
+        if ((rc = run_fitness_planned(ctx, s->st, (const float*)s->pop[0].p, (int64_t)KP, N, 9,
+                                      (const float4*)s->plan.p, (const float*)s->wpart.p, c.fitness_mode, c.H, c.W,
+                                      c.k_sigma, (float*)s->fits[0].p, P)))
+            return bail(rc);
+    } else if ((rc = run_fitness(ctx, s->st, (const float*)s->pop[0].p, (int64_t)KP, N, 9, (const float*)s->target.p,
+                                 mask_hw ? (const float*)s->mask.p : nullptr, c.fitness_mode, c.boost_beta,
+                                 c.H, c.W, c.k_sigma, (float*)s->fits[0].p, s->plan_id)))
         return bail(rc);
     double* row;
     if ((rc = gi_curves_row(s.get(), &row))) return bail(rc);
@@ -1724,6 +1841,20 @@ int ggs_ga_islands_create(int32_t device, const ggs_ga_config* cfg, const ggs_ga
     s->n_curves = 1;
     *handle = s.release();
     return GGS_OK;
+}
+}  // namespace
+}  // namespace ggs
+extern "C" {
+
+int ggs_ga_islands_create(int32_t device, const ggs_ga_config* cfg, const ggs_ga_islands* isl,
+                          const float* target_hw3, const float* mask_hw, const float* init_pops, void** handle) {
+    return ggs::gi_create(device, cfg, isl, target_hw3, mask_hw, init_pops, handle, false);
+}
+
+int ggs_ga_islands_create_targets(int32_t device, const ggs_ga_config* cfg, const ggs_ga_islands* isl,
+                                  const float* targets_khw3, const float* masks_khw, const float* init_pops,
+                                  void** handle) {
+    return ggs::gi_create(device, cfg, isl, targets_khw3, masks_khw, init_pops, handle, true);
 }
 
 int ggs_ga_islands_run(void* handle, int32_t first_gen, int32_t n_gens, int32_t total_gens) {

@@ -972,10 +972,16 @@ ga_migrate_rank_kernel(const float* __restrict__ fits, int P, int m, int* __rest
 // grid (m + 1, island).  Workgroup j < m copies emigrant j's genome; workgroup m
 // installs the immigrants' fitness and recomputes the island's elite list (the
 // breed's row map) from its new fitness vector.
+// Islands with a target each (ggs_ga_islands_create_targets) run it as two
+// launches around the immigrants' re-evaluation: grid (m, island) with `stage`
+// ([K][m][N][9]: the genomes also go there, compact, for the grouped fitness
+// launch), then grid (1, island) with j0 = m and `refit` ([K][m]: the immigrants'
+// fitness against island k's target, installed instead of the source island's).
 __global__ void __launch_bounds__(RANKMAX)
 ga_migrate_apply_kernel(float* __restrict__ pop, float* __restrict__ fits, int P, int N, int m, int elite_k,
-                        const int* __restrict__ mig, int* __restrict__ elite) {
-    const int j = blockIdx.x, k = blockIdx.y, K = gridDim.y;
+                        const int* __restrict__ mig, int* __restrict__ elite, int j0, float* __restrict__ stage,
+                        const float* __restrict__ refit) {
+    const int j = blockIdx.x + j0, k = blockIdx.y, K = gridDim.y;
     const int from_k = (k - 1 + K) % K;
     const int* __restrict__ best_from = mig + (int64_t)from_k * 2 * m;
     const int* __restrict__ worst_to = mig + (int64_t)k * 2 * m + m;
@@ -983,6 +989,15 @@ ga_migrate_apply_kernel(float* __restrict__ pop, float* __restrict__ fits, int P
     if (j < m) {
         const float* __restrict__ from = pop + ((int64_t)from_k * P + best_from[j]) * row;
         float* __restrict__ to = pop + ((int64_t)k * P + worst_to[j]) * row;
+        if (stage) {
+            float* __restrict__ sg = stage + ((int64_t)k * m + j) * row;
+            for (int64_t i = threadIdx.x; i < row; i += blockDim.x) {
+                const float v = from[i];
+                to[i] = v;
+                sg[i] = v;
+            }
+            return;
+        }
         for (int64_t i = threadIdx.x; i < row; i += blockDim.x) to[i] = from[i];
         return;
     }
@@ -992,7 +1007,7 @@ ga_migrate_apply_kernel(float* __restrict__ pop, float* __restrict__ fits, int P
     __syncthreads();
     // the emigrants' fitness: best-m rows of the neighbour, which nobody writes
     for (int q = threadIdx.x; q < m; q += blockDim.x) {
-        const float v = fits[(int64_t)from_k * P + best_from[q]];
+        const float v = refit ? refit[(int64_t)k * m + q] : fits[(int64_t)from_k * P + best_from[q]];
         key[worst_to[q]] = v;
         f[worst_to[q]] = v;
     }
@@ -1106,7 +1121,28 @@ hipError_t launch_ga_migrate(hipStream_t st, int K, float* pop, float* fits, int
     while (nt < P && nt < RANKMAX) nt <<= 1;
     hipLaunchKernelGGL(ga_migrate_rank_kernel, dim3(K), dim3(nt), 0, st, fits, P, m, mig);
     hipLaunchKernelGGL(ga_migrate_apply_kernel, dim3(m + 1, K), dim3(nt < 256 ? 256 : nt), 0, st, pop, fits, P, N, m,
-                       elite_k, mig, elite);
+                       elite_k, mig, elite, 0, (float*)nullptr, (const float*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_ga_migrate_copy(hipStream_t st, int K, float* pop, const float* fits, int P, int N, int m,
+                                  int* mig, float* stage) {
+    if (K < 2 || m < 1 || 2 * m > P || P > RANKMAX || !stage) return hipErrorInvalidValue;
+    int nt = 64;
+    while (nt < P && nt < RANKMAX) nt <<= 1;
+    hipLaunchKernelGGL(ga_migrate_rank_kernel, dim3(K), dim3(nt), 0, st, fits, P, m, mig);
+    hipLaunchKernelGGL(ga_migrate_apply_kernel, dim3(m, K), dim3(nt < 256 ? 256 : nt), 0, st, pop, (float*)nullptr, P,
+                       N, m, 0, mig, (int*)nullptr, 0, stage, (const float*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_ga_migrate_install(hipStream_t st, int K, float* fits, int P, int m, int elite_k, const int* mig,
+                                     const float* refit, int* elite) {
+    if (K < 2 || m < 1 || 2 * m > P || P > RANKMAX || !refit) return hipErrorInvalidValue;
+    int nt = 64;
+    while (nt < P && nt < RANKMAX) nt <<= 1;
+    hipLaunchKernelGGL(ga_migrate_apply_kernel, dim3(1, K), dim3(nt < 256 ? 256 : nt), 0, st, (float*)nullptr, fits, P,
+                       0, m, elite_k, mig, elite, m, (float*)nullptr, refit);
     return hipGetLastError();
 }
 

@@ -69,11 +69,14 @@ struct FinFused {
 };
 // simds: SIMDs of the launch's device (DevCtx::simds; 0 = unknown: no single-round
 // reordering).
+// group > 0: a plan set (launch_plan_set).  `plan` and fin->wpartials are those of
+// plan 0 and candidate b is scored against plan b / group; fitness only (mode 1),
+// without dirty / clean / live.
 hipError_t launch_raster(hipStream_t st, int mode, const SplatRec* recs, const int4* bnds, int B, int N, int H, int W,
                          const float bg[3], float* img, const float4* plan, float* partials,
                          const int* tile_order, const unsigned char* dirty = nullptr,
                          const float* clean = nullptr, const int* live = nullptr, const FinFused* fin = nullptr,
-                         int simds = 0);
+                         int simds = 0, int group = 0);
 // SIMDs (CUs x 4) of HIP device `dev`, 0 if unknown.
 int device_simds(int dev);
 
@@ -88,6 +91,11 @@ hipError_t launch_dirty(hipStream_t st, const float* curr, const float* nb, cons
 // wblock (plan_wsum_bytes): the plan's Sum w as a double, then per-wave sums.
 hipError_t launch_plan(hipStream_t st, const float* target, const float* mask, int mode, float beta,
                        int H, int W, float4* plan, float* wblock);
+// K plans of one (H, W, mode, beta) in one launch: targets [K][H][W][3], masks
+// [K][H][W] (or null), plans K * plan_bytes and wblocks K * plan_wsum_bytes, plan
+// k at those strides (launch_plan is K = 1).
+hipError_t launch_plan_set(hipStream_t st, const float* targets, const float* masks, int mode, float beta,
+                           int H, int W, int K, float4* plans, float* wblocks);
 size_t plan_bytes(int H, int W);
 size_t plan_wsum_bytes(int H, int W);
 // Tile visiting order for the raster grid: tiles sorted by distance of their
@@ -98,7 +106,8 @@ int raster_order_len(int H, int W);
 hipError_t launch_detmath(hipStream_t st, const float* x, const float* y, int64_t n, int fn,
                           float* out);
 hipError_t launch_finalize(hipStream_t st, const float* partials, const float* wpartials, int B,
-                           int nTiles, int mode, int H, int W, float* out, const int* live = nullptr);
+                           int nTiles, int mode, int H, int W, float* out, const int* live = nullptr,
+                           int group = 0);   // group > 0: wpartials of plan set entry b / group
 
 // ---- device GA (ggs_ga.hip) -------------------------------------------------
 struct GaParamsDev {            // one generation's operator parameters (float32 as the host path)
@@ -272,6 +281,15 @@ hipError_t launch_ga_gather_islands(hipStream_t st, int K, const float* pop, con
 // mig: [K][2 m] ints of scratch.  K >= 2, 1 <= m <= P / 2.
 hipError_t launch_ga_migrate(hipStream_t st, int K, float* pop, float* fits, int P, int N, int m, int elite_k,
                              int* mig, int* elite);
+// The same migration for islands with a target each, in two steps around the
+// immigrants' re-evaluation: _copy moves the genomes (and stages them compactly,
+// stage [K][m][N][9], immigrant j of island k at k * m + j); _install writes
+// refit [K][m], their fitness against island k's target, into the rows they
+// took and recomputes elite.
+hipError_t launch_ga_migrate_copy(hipStream_t st, int K, float* pop, const float* fits, int P, int N, int m,
+                                  int* mig, float* stage);
+hipError_t launch_ga_migrate_install(hipStream_t st, int K, float* fits, int P, int m, int elite_k, const int* mig,
+                                     const float* refit, int* elite);
 
 // ---- RCCL (ggs_comm.cpp) ----------------------------------------------------
 // Grouped in-place all-gather over single-process communicators (ggs_comm_init_local):

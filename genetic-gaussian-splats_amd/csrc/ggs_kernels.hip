@@ -115,6 +115,10 @@ constexpr int OCC = 3;            // waves per SIMD the register budget is sized
 // -0.5 %; at 1024^2/1024 (33 MB of records) the 8-group rotation is 0.6 % faster)
 constexpr int XCD_SHIFT = 3;
 constexpr int CULL_PRIO = 2;      // s_setprio while culling (1 and 3 measured the same)
+// A plan's weight block (plan_kernel): Sum w as a double in a 16-B slot, then one
+// float per plan wave, PLAN_Q waves per strip.  In floats; a plan set strides by it.
+constexpr int PLAN_Q = 4;
+__host__ __device__ constexpr int plan_wsum_floats(int nTiles) { return 4 + 4 * PLAN_Q * nTiles; }
 
 // Depth-split experiment (probe build only, docs/EXPERIMENTS.md §15): the fitness
 // instances without the saturation check (N <= SAT_MIN_SPLATS) run two waves per
@@ -335,14 +339,20 @@ __device__ __forceinline__ f2_t fma2(f2_t a, f2_t b, f2_t c) { return __builtin_
 // per step, highest index first, ballot + mbcnt compaction -> an order-
 // preserving LDS list), blends that list front-to-back, and writes its own
 // partial sum.  TILE_H = 128: 128 accumulator VGPRs (+~35) -> 3 waves per SIMD.
-template <int MODE, bool SAT, bool FUSED>
-__global__ void __launch_bounds__(GGS_DEPTH_SPLIT ? 2 * NT : NT, OCC)
-raster_kernel(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, int B, int N, int H, int W, int nTX,
-              int nTiles,
-              float bg_r, float bg_g, float bg_b, float* __restrict__ img,
-              const float4* __restrict__ plan, float* __restrict__ partials,
-              const int* __restrict__ tile_order, const unsigned char* __restrict__ dirty,
-              const float* __restrict__ clean, const int* __restrict__ live, int CH, FinFused fin, int simds) {
+//
+// raster_body is the one kernel body; its entry points are raster_kernel (one
+// target plan per launch) and raster_multi_kernel (a plan set: candidate b is
+// scored against plan b / group, MULTI).
+template <int MODE, bool SAT, bool FUSED, bool MULTI>
+__device__ __forceinline__ void
+raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, int B, int N, int H, int W, int nTX,
+            int nTiles,
+            float bg_r, float bg_g, float bg_b, float* __restrict__ img,
+            const float4* __restrict__ plan, float* __restrict__ partials,
+            const int* __restrict__ tile_order, const unsigned char* __restrict__ dirty,
+            const float* __restrict__ clean, const int* __restrict__ live, int CH, FinFused fin, int simds,
+            int group) {
+    static_assert(!MULTI || MODE == 1, "plan sets are for the fitness epilogue");
     constexpr bool DS = GGS_DEPTH_SPLIT && MODE == 1 && !SAT;
     // cull-list words carry the visit's scalar control (visit_word): the instances
     // without the saturation check and the folded finalize (in the GA's folded
@@ -403,6 +413,9 @@ raster_kernel(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, 
     // (the next group's block in the same XCD slot) then run the same candidate,
     // whose records stay in that XCD's caches across 8 groups (see XCD_SHIFT)
     const int b = b0 + (int)((idx + (gi >> (SAT ? XCD_SHIFT : 0))) % Bc);
+    // a plan set: the candidate's plan, divided here (the division's VALU temporaries
+    // would spill at the epilogue's register peak) and kept in one SGPR
+    const int pk = MULTI ? ufirst(b / group) : 0;
     const int t = grp / SPB;
     const int wv = (grp % SPB) * WPB + wib;           // strip 0..3 of the tile
     const int tx0 = (t % nTX) * TILE;
@@ -908,7 +921,13 @@ raster_kernel(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, 
         // (t_b, t_b', w, w'), w already mode-specific and 0 outside the image:
         // coalesced 16-B loads, no address math, no bounds tests, and the pair
         // lines up with the packed accumulators (two pixels per v_pk op).
-        const float4* __restrict__ P = plan + (int64_t)(t * 4 + wv) * RG * 64 + lane;
+        // A plan set (MULTI): K plans plan_bytes apart and K weight blocks
+        // plan_wsum_bytes apart (launch_plan_set); candidate b reads those of
+        // plan pk = b / group, a wave-uniform index kept on the scalar side.
+        // (the set's strips are numbered through, pk * nTiles * 4 + the plan's own:
+        // the single plan's address arithmetic)
+        if (MULTI) fin.wpartials += (int64_t)pk * plan_wsum_floats(nTiles);
+        const float4* __restrict__ P = plan + (int64_t)((MULTI ? pk * nTiles + t : t) * 4 + wv) * RG * 64 + lane;
         f2_t accp = 0.0f;
         // background pairs (bg, bg) in SGPR pairs: no VGPRs at the epilogue's peak
         const uint64_t bg2r = (uint64_t)__float_as_uint(bg_r) * 0x100000001ull;
@@ -956,6 +975,32 @@ raster_kernel(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, 
 #endif
 }
 
+template <int MODE, bool SAT, bool FUSED>
+__global__ void __launch_bounds__(GGS_DEPTH_SPLIT ? 2 * NT : NT, OCC)
+raster_kernel(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, int B, int N, int H, int W, int nTX,
+              int nTiles,
+              float bg_r, float bg_g, float bg_b, float* __restrict__ img,
+              const float4* __restrict__ plan, float* __restrict__ partials,
+              const int* __restrict__ tile_order, const unsigned char* __restrict__ dirty,
+              const float* __restrict__ clean, const int* __restrict__ live, int CH, FinFused fin, int simds) {
+    raster_body<MODE, SAT, FUSED, false>(recs, bnds, B, N, H, W, nTX, nTiles, bg_r, bg_g, bg_b, img, plan, partials,
+                                         tile_order, dirty, clean, live, CH, fin, simds, 1);
+}
+
+// The fitness raster against a plan set: `plan` and fin.wpartials are those of
+// plan 0, candidate b reads plan b / group (group >= 1).  No image, no
+// incremental (dirty) strips and no live count: the arguments it does not take
+// leave it the SGPRs for `group`.
+template <bool SAT, bool FUSED>
+__global__ void __launch_bounds__(GGS_DEPTH_SPLIT ? 2 * NT : NT, OCC)
+raster_multi_kernel(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, int B, int N, int H, int W,
+                    int nTX, int nTiles, float bg_r, float bg_g, float bg_b, const float4* __restrict__ plan,
+                    float* __restrict__ partials, const int* __restrict__ tile_order, int CH, FinFused fin,
+                    int simds, int group) {
+    raster_body<1, SAT, FUSED, true>(recs, bnds, B, N, H, W, nTX, nTiles, bg_r, bg_g, bg_b, nullptr, plan, partials,
+                                     tile_order, nullptr, nullptr, nullptr, CH, fin, simds, group);
+}
+
 // ---------------------------------------------------------------------------
 // target plan: the fitness epilogue's inputs re-laid out in raster lane order
 // ---------------------------------------------------------------------------
@@ -969,11 +1014,18 @@ raster_kernel(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, 
 // the image.  Each wave's sum of w goes to the weight block (plan_wsum_kernel
 // reduces them to the plan's Sum w, a double).  Target and mask are constant
 // over a GA run, so the plan is built once per (target, mask, mode, beta).
-constexpr int PLAN_Q = 4, PLAN_KP = RG / 2 / PLAN_Q;
+constexpr int PLAN_KP = RG / 2 / PLAN_Q;
 __global__ void __launch_bounds__(64)
 plan_kernel(const float* __restrict__ target, const float* __restrict__ mask, int mode, float beta,
-            int H, int W, int nTX, float4* __restrict__ plan, float* __restrict__ wave_w) {
+            int H, int W, int nTX, float4* __restrict__ plan, float* __restrict__ wave_w, int nTiles) {
     const int lane = threadIdx.x;
+    // a plan set (grid.y = K): plan blockIdx.y of K targets / masks / plans / weight blocks, each contiguous
+    if (const int64_t pk = blockIdx.y) {
+        target += pk * H * W * 3;
+        if (mask) mask += pk * H * W;
+        plan += pk * nTiles * (4 * RG * 64);
+        wave_w += pk * plan_wsum_floats(nTiles);
+    }
     const int sg = blockIdx.x / PLAN_Q, q = blockIdx.x % PLAN_Q;     // strip (t*4 + wv), quarter
     const int t = sg >> 2, wv = sg & 3;
     const int tx0 = (t % nTX) * TILE, ty0 = (t / nTX) * TILE_H;
@@ -1009,23 +1061,30 @@ plan_kernel(const float* __restrict__ target, const float* __restrict__ mask, in
 // butterfly of wave_sum): the weighted / boost modes' denominator
 // (fitness.py:23-31), once per plan instead of once per candidate.
 __global__ void __launch_bounds__(64)
-plan_wsum_kernel(const float* __restrict__ wave_w, int n, double* __restrict__ wsum) {
-    const double v = wave_sum(wave_w, n);
-    if (threadIdx.x == 0) *wsum = v;
+plan_wsum_kernel(float* wblock, int n) {    // one workgroup per plan of the set
+    float* wb = wblock + (int64_t)blockIdx.x * (4 + n);
+    const double v = wave_sum(wb + 4, n);                       // after the double (16-B slot)
+    if (threadIdx.x == 0) *reinterpret_cast<double*>(wb) = v;
+}
+
+hipError_t launch_plan_set(hipStream_t st, const float* targets, const float* masks, int mode, float beta,
+                           int H, int W, int K, float4* plans, float* wblocks) {
+    int nTX;
+    const int nTiles = raster_tiles(H, W, &nTX);
+    const int nw = nTiles * 4 * PLAN_Q;
+    float* wave_w = wblocks + 4;                 // after the double (16-B slot)
+    hipLaunchKernelGGL(plan_kernel, dim3(nw, K), dim3(64), 0, st, targets, masks, mode, beta, H, W, nTX, plans,
+                       wave_w, nTiles);
+    hipLaunchKernelGGL(plan_wsum_kernel, dim3(K), dim3(64), 0, st, wblocks, nw);
+    return hipGetLastError();
 }
 
 hipError_t launch_plan(hipStream_t st, const float* target, const float* mask, int mode, float beta,
                        int H, int W, float4* plan, float* wblock) {
-    int nTX;
-    const int nTiles = raster_tiles(H, W, &nTX);
-    const int nw = nTiles * 4 * PLAN_Q;
-    float* wave_w = wblock + 4;                  // after the double (16-B slot)
-    hipLaunchKernelGGL(plan_kernel, dim3(nw), dim3(64), 0, st, target, mask, mode, beta, H, W, nTX, plan, wave_w);
-    hipLaunchKernelGGL(plan_wsum_kernel, dim3(1), dim3(64), 0, st, wave_w, nw, reinterpret_cast<double*>(wblock));
-    return hipGetLastError();
+    return launch_plan_set(st, target, mask, mode, beta, H, W, 1, plan, wblock);
 }
 
-size_t plan_wsum_bytes(int H, int W) { return 16 + sizeof(float) * 4 * PLAN_Q * (size_t)raster_tiles(H, W, nullptr); }
+size_t plan_wsum_bytes(int H, int W) { return sizeof(float) * (size_t)plan_wsum_floats(raster_tiles(H, W, nullptr)); }
 
 // ---------------------------------------------------------------------------
 // dirty strips (incremental SA evaluation, SURVEY.md §8f #4 / annealing.py:121-146)
@@ -1094,9 +1153,12 @@ size_t plan_bytes(int H, int W) { return sizeof(float4) * 4 * (size_t)raster_til
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 finalize_kernel(const float* __restrict__ partials, const float* __restrict__ wpartials,
-                int nTiles, int mode, double hw, int B, float* __restrict__ out, const int* __restrict__ live) {
+                int nTiles, int mode, double hw, int B, float* __restrict__ out, const int* __restrict__ live,
+                int group) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);   // one wave per candidate (ggs_prep.h)
     if (b >= B || (live && b >= *live)) return;
+    // a plan set: the weight block of plan b / group (nTiles here counts strips, 4 per tile)
+    if (group > 0) wpartials += (int64_t)(b / group) * (4 + PLAN_Q * nTiles);
     const float v = finalize_wave(partials, wpartials, nTiles, mode, hw, b);
     if ((threadIdx.x & 63) == 0) out[b] = v;
 }
@@ -1201,7 +1263,7 @@ int device_simds(int dev) {
 hipError_t launch_raster(hipStream_t st, int mode, const SplatRec* recs, const int4* bnds, int B, int N, int H, int W,
                          const float bg[3], float* img, const float4* plan, float* partials,
                          const int* tile_order, const unsigned char* dirty, const float* clean,
-                         const int* live, const FinFused* fin, int simds) {
+                         const int* live, const FinFused* fin, int simds, int group) {
     int nTX;
     const int nTiles = raster_tiles(H, W, &nTX);
     const dim3 grid((unsigned)((int64_t)B * nTiles * SPB)), block(NT);
@@ -1217,18 +1279,27 @@ hipError_t launch_raster(hipStream_t st, int mode, const SplatRec* recs, const i
                        bg[0], bg[1], bg[2], img, plan, partials, tile_order, dirty, clean, live, CH, ff, simds)
     // the saturation check only where strip lists can grow long (N > SAT_MIN_SPLATS);
     // at the bench's 256 splats the kernel without it is the faster code (+1.6 %)
-    if (mode == 0) { if (!sat) GGS_RASTER(0, false, false); else GGS_RASTER(0, true, false); }   // image
+#define GGS_RASTER_MULTI(S, F)                                                                 \
+    hipLaunchKernelGGL((raster_multi_kernel<S, F>), grid, block_f, 0, st, recs, bnds, B, N, H, W, nTX, nTiles, bg[0], \
+                       bg[1], bg[2], plan, partials, tile_order, CH, ff, simds, group)
+    if (group > 0) {   // a plan set: the separately named entry points, fitness only
+        if (mode != 1 || dirty || clean || live) return hipErrorInvalidValue;
+        if (!ff.ctr) { if (!sat) GGS_RASTER_MULTI(false, false); else GGS_RASTER_MULTI(true, false); }
+        else { if (!sat) GGS_RASTER_MULTI(false, true); else GGS_RASTER_MULTI(true, true); }
+    }
+    else if (mode == 0) { if (!sat) GGS_RASTER(0, false, false); else GGS_RASTER(0, true, false); }   // image
     else if (!ff.ctr) { if (!sat) GGS_RASTER(1, false, false); else GGS_RASTER(1, true, false); }   // fitness
     else { if (!sat) GGS_RASTER(1, false, true); else GGS_RASTER(1, true, true); }  // + folded finalize
+#undef GGS_RASTER_MULTI
 #undef GGS_RASTER
     return hipGetLastError();
 }
 
 hipError_t launch_finalize(hipStream_t st, const float* partials, const float* wpartials, int B,
-                           int nTiles, int mode, int H, int W, float* out, const int* live) {
+                           int nTiles, int mode, int H, int W, float* out, const int* live, int group) {
     // 4 strip partials per (candidate, tile)
     hipLaunchKernelGGL(finalize_kernel, dim3((B + 3) / 4), dim3(256), 0, st, partials, wpartials, nTiles * 4,
-                       mode, (double)H * (double)W, B, out, live);
+                       mode, (double)H * (double)W, B, out, live, group);
     return hipGetLastError();
 }
 

@@ -75,6 +75,11 @@ SIGNATURES = {
     "ggs_fitness_device_planned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                              C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "ggs_plan_destroy": (None, [C.c_void_p]),
+    "ggs_planset_create": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_float, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "ggs_fitness_device_planset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    "ggs_planset_destroy": (None, [C.c_void_p]),
     "ggs_ga_create": (C.c_int, [C.c_int32, C.POINTER(GaConfig), _f32p, _f32p, _f32p,
                                 C.POINTER(C.c_void_p)]),
     "ggs_ga_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(GaDraws)]),
@@ -83,6 +88,8 @@ SIGNATURES = {
     "ggs_ga_destroy": (None, [C.c_void_p]),
     "ggs_ga_islands_create": (C.c_int, [C.c_int32, C.POINTER(GaConfig), C.POINTER(GaIslands), _f32p,
                                         _f32p, _f32p, C.POINTER(C.c_void_p)]),
+    "ggs_ga_islands_create_targets": (C.c_int, [C.c_int32, C.POINTER(GaConfig), C.POINTER(GaIslands), _f32p,
+                                                _f32p, _f32p, C.POINTER(C.c_void_p)]),
     "ggs_ga_islands_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "ggs_ga_islands_read": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f64p, _f64p, _i32p]),
     "ggs_ga_islands_destroy": (None, [C.c_void_p]),

@@ -235,6 +235,39 @@ class TargetPlan:
             pass
 
 
+class TargetPlanSet:
+    """K targets/masks of one (H, W, mode, beta) prepared once (``ggs_planset_*``):
+    ``d_targets`` [K, H, W, 3] and ``d_masks`` [K, H, W] (0 for mode 0) are device
+    pointers on ``device``.  ``fitness_device`` scores candidate b against plan
+    ``b // group`` in one launch sequence: a folder of images, the frames of a clip
+    or the tiles of a picture evaluated as one batch."""
+
+    def __init__(self, device: int, stream: int, d_targets: int, d_masks: int, mode: int,
+                 boost_beta: float, H: int, W: int, K: int):
+        h = C.c_void_p()
+        check(lib.ggs_planset_create(device, C.c_void_p(stream), C.c_void_p(d_targets or None),
+                                     C.c_void_p(d_masks or None), mode, float(boost_beta), H, W, K,
+                                     C.byref(h)), "ggs_planset_create")
+        self.h, self.H, self.W, self.K = h, H, W, K
+
+    def fitness_device(self, stream: int, d_genomes: int, B: int, N: int, Cc: int, group: int,
+                       k_sigma: float, d_out: int) -> None:
+        check(lib.ggs_fitness_device_planset(self.h, C.c_void_p(stream), C.c_void_p(d_genomes or None), B,
+                                             N, Cc, group, float(k_sigma), C.c_void_p(d_out or None)),
+              "ggs_fitness_device_planset")
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            lib.ggs_planset_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 — interpreter shutdown
+            pass
+
+
 def render_device(device: int, stream: int, d_genomes: int, B: int, N: int, Cc: int, H: int,
                   W: int, k_sigma: float, d_out: int, background=(1.0, 1.0, 1.0)) -> None:
     bg = np.ascontiguousarray(np.broadcast_to(np.asarray(background, np.float32), (3,)))

@@ -354,13 +354,19 @@ def save_loss_curve_png(curves, out_path: str, title: str = "GA fitness over gen
     fig.savefig(out_path, dpi=dpi)
 
 
-def ring_migration(pops: np.ndarray, fits: np.ndarray, m: int):
+def ring_migration(pops: np.ndarray, fits: np.ndarray, m: int, refit=None):
     """One ring migration of an island group on the host (the definition the
     device applies, include/ggs.h): with every island ranked by fitness
     (ascending, ties by lower row), the row of rank j < m of island (k - 1) mod K
     overwrites the row of rank P - 1 - j of island k, genome and fitness, all
     islands at once from the pre-migration state.  ``pops`` [K, P, N, 9],
-    ``fits`` [K, P]; returns new arrays.  K < 2 or m == 0: copies."""
+    ``fits`` [K, P]; returns new arrays.  K < 2 or m == 0: copies.
+
+    ``refit`` (islands with a target each): ``refit(k, genomes [m, N, 9]) -> [m]``
+    gives the immigrants' fitness on island k, in the order j = 0 .. m - 1 (the
+    source island's ranks); it is installed instead of the fitness the rows had
+    on their source island, whose target it was measured against.  Which rows
+    move is decided from the pre-migration fitness either way."""
     pops, fits = np.asarray(pops), np.asarray(fits)
     K, P = fits.shape
     if not 0 <= m <= P // 2:
@@ -374,6 +380,9 @@ def ring_migration(pops: np.ndarray, fits: np.ndarray, m: int):
         for j in range(m):
             new_p[k, order[k][P - 1 - j]] = pops[src, order[src][j]]
             new_f[k, order[k][P - 1 - j]] = fits[src, order[src][j]]
+        if refit is not None:
+            rows = [order[k][P - 1 - j] for j in range(m)]
+            new_f[k, rows] = np.asarray(refit(k, new_p[k, rows]), new_f.dtype).reshape(m)
     return new_p, new_f
 
 
@@ -540,6 +549,88 @@ def genetic_approx(target_img_uint8, H: int, W: int, device, pop_size: int, n_sp
     if return_state:
         return best_ind, best_fit, {"population": pop, "fitness": fits, "curves": curves}
     return best_ind, best_fit
+
+
+def genetic_approx_many(images, H: int, W: int, device, pop_size: int, n_splats: int,
+                        generations: int, tour_k: int, elite_k: int, cxpb: float, mutpb: float,
+                        mut_sigma_max: dict, mut_sigma_min: dict, schedule: str,
+                        min_scale_splats: float, max_scale_splats: float, k_sigma: float,
+                        mask_strength: float, boost_only: bool, *, seed: Optional[int] = None,
+                        migrate_every: int = 0, migrants: int = 0,
+                        init_population: Optional[np.ndarray] = None, chunk: int = 50,
+                        progress: bool = True, return_state: bool = False):
+    """``genetic_approx`` (device backend) for K images in one session: an island
+    group with a target per island (``ga_device.DeviceGAIslands`` with a 4-D
+    target), one breed and one raster launch per generation for all K.
+
+    Each image goes through ``prepare_target`` and ``compute_importance_mask`` as
+    in ``genetic_approx``; image k is seeded ``(seed + k) mod 2^64`` and starts
+    from ``new_population(..., default_rng(seed_k))`` (``init_population``, when
+    given, is [K, P, N, 9]).  With ``migrate_every`` == 0 image k's result is that
+    of ``genetic_approx(images[k], ..., seed=seed + k, backend="device")``, bit for
+    bit; with migration the ``migrants`` best of image k - 1's population are
+    re-scored against image k before they replace its worst (neighbouring frames
+    or tiles seed each other).
+
+    Returns a list of K ``(best individual [N, 9], best fitness)``; with
+    ``return_state`` each entry is ``(best, best_fit, {"population", "fitness",
+    "curves"})``.  No frames, CSV or PNG outputs."""
+    from . import api
+    from .ga_device import run_device_ga_islands
+    from .mask import compute_importance_mask, prepare_target
+
+    images = list(images)
+    K = len(images)
+    if K < 1:
+        raise ValueError("genetic_approx_many needs at least one image")
+    seed = resolve_seed(seed)
+    seeds = [(seed + k) % 2**64 for k in range(K)]
+    targets = np.stack([prepare_target(im, H, W) for im in images])
+    masks = np.stack([compute_importance_mask(t, H, W, edge_scales=(1, 2, 4), w_edge=0.7, w_var=0.3,
+                                              gamma=0.7, floor=0.15, smooth=3, strength=mask_strength)
+                      for t in targets])
+    if init_population is not None:
+        pops = np.array(init_population, np.float32, copy=True)
+        if pops.ndim != 4 or pops.shape[0] != K:
+            raise ValueError(f"init_population must be [K={K}, P, N, 9], got {pops.shape}")
+    else:
+        pops = np.stack([new_population(pop_size, n_splats, H, W, min_scale_splats, max_scale_splats,
+                                        np.random.default_rng(sk)) for sk in seeds])
+    bar = None
+    if progress:
+        try:
+            from tqdm.auto import tqdm
+            bar = tqdm(total=generations, desc=f"GA generations (device, {K} images)", leave=True)
+        except ImportError:
+            pass
+    state = {"gen": 0}
+
+    def on_chunk(gen, ga):
+        if bar is not None:
+            bar.update(gen - state["gen"])
+        state["gen"] = gen
+
+    try:
+        st = run_device_ga_islands(targets, masks, pops, seeds, generations,
+                                   migrate_every=int(migrate_every), n_migrants=int(migrants),
+                                   tour_k=tour_k, elite_k=elite_k, cxpb=cxpb, mutpb=mutpb,
+                                   mut_sigma_max=mut_sigma_max, mut_sigma_min=mut_sigma_min,
+                                   schedule=schedule, min_scale_splats=min_scale_splats,
+                                   max_scale_splats=max_scale_splats, k_sigma=k_sigma,
+                                   boost_only=boost_only, chunk=max(1, chunk), on_chunk=on_chunk,
+                                   device=api.device_index(device))
+    finally:
+        if bar is not None:
+            bar.close()
+    out = []
+    for k in range(K):
+        best, bf = st["best"][k], float(st["best_fit"][k])
+        if return_state:
+            out.append((best, bf, {"population": st["population"][k], "fitness": st["fitness"][k],
+                                   "curves": st["curves"][k]}))
+        else:
+            out.append((best, bf))
+    return out
 
 
 def _genetic_approx_device(t, imp_mask, pop, H, W, generations, tour_k, elite_k, cxpb, mutpb,

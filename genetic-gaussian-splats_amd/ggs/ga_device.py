@@ -237,7 +237,13 @@ class DeviceGAIslands:
     launch per generation for all islands.  ``init_pops`` is [K, P, N, 9],
     ``seeds`` [K]; island k without migration follows ``DeviceGA(seed=seeds[k],
     init_pop=init_pops[k])`` bit for bit.  Every ``migrate_every`` generations the
-    ``n_migrants`` best rows of island k-1 replace the worst rows of island k."""
+    ``n_migrants`` best rows of island k-1 replace the worst rows of island k.
+
+    A 4-D ``target`` [K, H, W, 3] (with ``mask`` [K, H, W] or None) gives every
+    island its own image (ggs_ga_islands_create_targets): island k is fitted to
+    ``target[k]``, and an immigrant is re-scored against its new island's target
+    and mask before the elites are re-ranked (``ggs.ga.ring_migration`` with
+    ``refit``).  A 3-D target is shared by all islands."""
 
     def __init__(self, target, mask, init_pops, seeds, migrate_every: int = 0, n_migrants: int = 0,
                  *, tour_k: int, elite_k: int, cxpb: float, mutpb: float,
@@ -253,8 +259,18 @@ class DeviceGAIslands:
         if sd.shape != (K,):
             raise _lib.GGSInputError(f"seeds must have one entry per island ({K}), got {sd.shape}")
         self.target = _arr(target, np.float32)
-        H, W = self.target.shape[:2]
         self.mask = None if mask is None else _arr(mask, np.float32)
+        self.per_island = self.target.ndim == 4
+        if self.per_island:
+            if self.target.shape[0] != K or self.target.shape[3] != 3:
+                raise _lib.GGSInputError(
+                    f"per-island targets must be [K={K}, H, W, 3], got {self.target.shape}")
+            if self.mask is not None and self.mask.shape != self.target.shape[:3]:
+                raise _lib.GGSInputError(
+                    f"per-island masks must be {self.target.shape[:3]}, got {self.mask.shape}")
+        elif self.target.ndim != 3:
+            raise _lib.GGSInputError(f"target must be [H, W, 3] or [K, H, W, 3], got {self.target.shape}")
+        H, W = self.target.shape[-3:-1]
         cfg = _config(P, N, H, W, tour_k, elite_k, cxpb, mutpb, k_sigma, min_scale_splats,
                       max_scale_splats, self.mask, boost_only, boost_beta, schedule,
                       mut_sigma_max, mut_sigma_min, 0)
@@ -263,10 +279,11 @@ class DeviceGAIslands:
         self.K, self.P, self.N, self.H, self.W = K, P, N, H, W
         h = C.c_void_p()
         # arguments are validated before the library looks for a device
-        check(lib.ggs_ga_islands_create(device, C.byref(cfg), C.byref(isl),
-                                        self.target.ctypes.data_as(_f32p),
-                                        None if self.mask is None else self.mask.ctypes.data_as(_f32p),
-                                        pops.ctypes.data_as(_f32p), C.byref(h)), "ggs_ga_islands_create")
+        create, name = ((lib.ggs_ga_islands_create_targets, "ggs_ga_islands_create_targets")
+                        if self.per_island else (lib.ggs_ga_islands_create, "ggs_ga_islands_create"))
+        check(create(device, C.byref(cfg), C.byref(isl), self.target.ctypes.data_as(_f32p),
+                     None if self.mask is None else self.mask.ctypes.data_as(_f32p),
+                     pops.ctypes.data_as(_f32p), C.byref(h)), name)
         self.h = h
 
     def run(self, first_gen: int, n_gens: int, total: int) -> None:

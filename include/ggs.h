@@ -126,6 +126,20 @@ int ggs_fitness_device_planned(void* plan, void* stream, const float* d_genomes_
                                int32_t N, int32_t C, float k_sigma, float* d_out_B);
 void ggs_plan_destroy(void* plan);
 
+/* Plan set: K target plans of one (H, W, mode, beta), built in one launch from
+ * d_targets_khw3 [K,H,W,3] and d_masks_khw [K,H,W] (required unless mode is
+ * GGS_FIT_NONE).  ggs_fitness_device_planset scores candidate b against plan
+ * b / group in one prep / raster / finalize: group >= 1, B % group == 0 and
+ * B / group <= K (fewer groups than plans use the first plans).  A candidate's
+ * fitness has the bits ggs_fitness_device_planned gives it against that plan
+ * alone.  Invalid arguments (those, K < 1, null pointers) are reported
+ * (GGS_EINVAL) before any device is touched. */
+int ggs_planset_create(int32_t device, void* stream, const float* d_targets_khw3, const float* d_masks_khw,
+                       int32_t mode, float boost_beta, int32_t H, int32_t W, int32_t K, void** planset);
+int ggs_fitness_device_planset(void* planset, void* stream, const float* d_genomes_axes, int64_t B,
+                               int32_t N, int32_t C, int32_t group, float k_sigma, float* d_out_B);
+void ggs_planset_destroy(void* planset);
+
 /* ---- device-resident GA ------------------------------
  * genetic_approx's generation loop (algorithm.py:85-155) on one device: the
  * population, fitness, elites, best individual and curves stay in HBM; a
@@ -214,6 +228,24 @@ typedef struct ggs_ga_islands {
 int ggs_ga_islands_create(int32_t device, const ggs_ga_config* cfg, const ggs_ga_islands* isl,
                           const float* target_hw3, const float* mask_hw,
                           const float* init_pops /* [K,P,N,9] */, void** handle);
+/* A target per island: targets_khw3 [K,H,W,3], masks_khw [K,H,W] (NULL iff
+ * fitness_mode is GGS_FIT_NONE); island k is fitted to image k (K images, the
+ * frames of a clip, the tiles of a picture in one session).  One plan set, and
+ * still one breed and one raster launch per generation: candidate k (P - E) + o
+ * is scored against plan k.  Without migration island k follows bit for bit
+ * the ggs_ga_create session on (targets[k], masks[k], seeds[k], init_pops[k]).
+ * Migration moves the same rows as above, but an immigrant's fitness was
+ * measured against its SOURCE island's image, so it is RE-SCORED: the genome
+ * is copied, the K m immigrants are evaluated against their destination
+ * island's target and mask (one prep and one grouped raster launch), that
+ * fitness is installed in the rows they took, and only then are island k's
+ * elites re-ranked from the new fitness vector.  (With K copies of one target
+ * this installs exactly the fitness the shared-target group copies.)
+ * Best-so-far and curves are not touched, as above.  Run, read and destroy are
+ * ggs_ga_islands_run / _read / _destroy. */
+int ggs_ga_islands_create_targets(int32_t device, const ggs_ga_config* cfg, const ggs_ga_islands* isl,
+                                  const float* targets_khw3, const float* masks_khw,
+                                  const float* init_pops /* [K,P,N,9] */, void** handle);
 int ggs_ga_islands_run(void* handle, int32_t first_gen, int32_t n_gens, int32_t total_gens);
 /* Synchronises; any output may be NULL: pop [K,P,N,9], fits [K,P], best_ind [K,N,9],
  * best_fit [K], curves [K][n_curves][3], n_curves (the same for every island). */
