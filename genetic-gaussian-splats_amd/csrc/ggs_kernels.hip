@@ -54,8 +54,15 @@ using namespace detmath;
 // ---------------------------------------------------------------------------
 // prep (per-splat math in ggs_prep.h, shared with the GA's fused variation)
 // ---------------------------------------------------------------------------
+// One wave per workgroup: under concurrent streams a raster wave (162-166 VGPRs,
+// 3 per SIMD) that ends is replaced at once by the next one-wave raster workgroup,
+// so a 4-wave workgroup waits until one CU has four slots free at once, until every
+// raster in flight has dispatched its whole grid (4 streams: prep up to 276 us,
+// finalize 269 us from dispatch to end); a lone 44-VGPR wave fits any slot a strip
+// wave frees (17.7 / 5.7 us; headline +0.9 %, docs/EXPERIMENTS.md §19).
+constexpr int PREP_THREADS = 64;
 template <bool ENCODE>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(PREP_THREADS)
 prep_kernel(const float* __restrict__ genomes, int64_t S, int C, int H, int W, float k,
             SplatRec* __restrict__ recs, int4* __restrict__ bnds, float* __restrict__ f9, int* __restrict__ i4,
             float* __restrict__ enc9, const int* __restrict__ live, int n_per) {
@@ -1151,16 +1158,18 @@ size_t plan_bytes(int H, int W) { return sizeof(float4) * 4 * (size_t)raster_til
 // ---------------------------------------------------------------------------
 // finalize: fixed-order float64 reduction of tile partials -> fitness scalar
 // ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(64)
 finalize_kernel(const float* __restrict__ partials, const float* __restrict__ wpartials,
                 int nTiles, int mode, double hw, int B, float* __restrict__ out, const int* __restrict__ live,
                 int group) {
-    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);   // one wave per candidate (ggs_prep.h)
+    // one wave per candidate (ggs_prep.h), one candidate per workgroup: a lone wave
+    // starts in any slot a concurrent raster's strip wave frees (see prep_kernel)
+    const int b = blockIdx.x;
     if (b >= B || (live && b >= *live)) return;
     // a plan set: the weight block of plan b / group (nTiles here counts strips, 4 per tile)
     if (group > 0) wpartials += (int64_t)(b / group) * (4 + PLAN_Q * nTiles);
     const float v = finalize_wave(partials, wpartials, nTiles, mode, hw, b);
-    if ((threadIdx.x & 63) == 0) out[b] = v;
+    if (threadIdx.x == 0) out[b] = v;
 }
 
 // ---------------------------------------------------------------------------
@@ -1199,7 +1208,7 @@ hipError_t launch_prep(hipStream_t st, bool encode, const float* genomes, int64_
                        int W, float k, SplatRec* recs, int4* bnds, float* f9, int* i4, float* enc9, const int* live,
                        int n_per) {
     if (S <= 0) return hipSuccess;
-    constexpr int PB = 256;           // 64-thread blocks (all CUs busy): no change, round 3
+    constexpr int PB = PREP_THREADS;  // (round 3's "64-thread blocks: no change" was one stream, nothing competing)
     const unsigned grid = (unsigned)((S + PB - 1) / PB);
     if (encode)
         hipLaunchKernelGGL(prep_kernel<true>, dim3(grid), dim3(PB), 0, st, genomes, S, C, H, W, k,
@@ -1298,7 +1307,7 @@ hipError_t launch_raster(hipStream_t st, int mode, const SplatRec* recs, const i
 hipError_t launch_finalize(hipStream_t st, const float* partials, const float* wpartials, int B,
                            int nTiles, int mode, int H, int W, float* out, const int* live, int group) {
     // 4 strip partials per (candidate, tile)
-    hipLaunchKernelGGL(finalize_kernel, dim3((B + 3) / 4), dim3(256), 0, st, partials, wpartials, nTiles * 4,
+    hipLaunchKernelGGL(finalize_kernel, dim3(B), dim3(64), 0, st, partials, wpartials, nTiles * 4,
                        mode, (double)H * (double)W, B, out, live, group);
     return hipGetLastError();
 }

@@ -26,7 +26,7 @@ with open(sys.argv[2], "w", newline="") as f:
                     int(r["End_Timestamp"]) - int(r["Start_Timestamp"])])
 PY
 done
-cp "$SRC/commands.txt" "$DST/"
+sed "s#$SRC/##g" "$SRC/commands.txt" > "$DST/commands.txt"   # output paths relative to the scratch folder
 # stamp the git revision: only when this tree's libggs.so is the profiled build
 python3 - "$SRC/summary.json" "$DST/summary.json" <<'PY'
 import hashlib, json, subprocess, sys
