@@ -131,6 +131,7 @@ int ensure_pinned(PinBuf& b, size_t bytes) {
 struct Workspace {
     hipStream_t stream = nullptr;
     DevBuf recs, bnds, partials, wpartials, order, plan, fctr;   // fctr: fused-finalize counters
+    DevBuf maskws;                    // target preparation / importance mask scratch (ggs_mask.hip)
     int order_H = -1, order_W = -1;   // (H, W) the tile order was built for
     uint64_t plan_key = 0;            // inputs the plan was built from (0: none / volatile)
 };
@@ -169,6 +170,7 @@ struct DevCtx {
     std::vector<std::unique_ptr<Workspace>> ws;
     // host-API staging
     DevBuf gen, out, target, mask;
+    DevBuf prep_in, prep_tgt, prep_mask;   // ggs_targets_prepare / ggs_quantiles staging
     PinBuf h_out;                  // the fitness scalars (render and genomes go straight to / from the caller)
     uint64_t target_key = 0, mask_key = 0;
     size_t target_bytes = 0, mask_bytes = 0;
@@ -588,10 +590,10 @@ void ggs_shutdown(void) {
         (void)hipStreamSynchronize(c->stream);
         for (auto& w : c->ws) {
             if (w->stream) (void)hipStreamSynchronize(w->stream);
-            for (DevBuf* b : {&w->recs, &w->bnds, &w->partials, &w->wpartials, &w->order, &w->plan, &w->fctr})
+            for (DevBuf* b : {&w->recs, &w->bnds, &w->partials, &w->wpartials, &w->order, &w->plan, &w->fctr, &w->maskws})
                 if (b->p) (void)hipFree(b->p);
         }
-        for (DevBuf* b : {&c->gen, &c->out, &c->target, &c->mask})
+        for (DevBuf* b : {&c->gen, &c->out, &c->target, &c->mask, &c->prep_in, &c->prep_tgt, &c->prep_mask})
             if (b->p) (void)hipFree(b->p);
         for (PinBuf* b : {&c->h_out})
             if (b->p) (void)hipHostFree(b->p);
@@ -761,6 +763,111 @@ void ggs_planset_destroy(void* planset) {
         if (p->wpartials.p) (void)hipFree(p->wpartials.p);
     }
     delete p;
+}
+
+// ---- target preparation and importance mask ------------------------------------
+}  // extern "C"
+namespace ggs {
+namespace {
+int check_prepare(const void* images, int32_t K, int32_t H0, int32_t W0, int32_t H, int32_t W,
+                  const ggs_mask_params* p, const void* targets, const void* masks) {
+    if (K < 1 || K > 65535) return fail(GGS_EINVAL, "K=%d images: must be in 1..65535", K);
+    if (!images || !targets) return fail(GGS_EINVAL, "null images / targets pointer");
+    if (p && !masks) return fail(GGS_EINVAL, "null masks pointer (params given)");
+    if (!p && masks) return fail(GGS_EINVAL, "masks wanted without params (params == NULL: targets only)");
+    if (H0 < 1 || W0 < 1 || H < 1 || W < 1)
+        return fail(GGS_EINVAL, "H0=%d, W0=%d, H=%d, W=%d must be >= 1", H0, W0, H, W);
+    if ((int64_t)H * W >= ((int64_t)1 << 29) || (int64_t)H0 * W0 >= ((int64_t)1 << 29))
+        return fail(GGS_EINVAL, "image of %lld or %lld pixels exceeds the limit 2^29", (long long)H0 * W0,
+                    (long long)H * W);
+    if (!p) return GGS_OK;
+    if (std::min(H, W) < 4) return fail(GGS_EINVAL, "min(H, W) = %d: the mask needs at least 4", std::min(H, W));
+    if (p->n_scales < 1 || p->n_scales > 4) return fail(GGS_EINVAL, "n_scales=%d must be in 1..4", p->n_scales);
+    for (int i = 0; i < p->n_scales; ++i) {
+        const int s = p->edge_scales[i];
+        if (s < 1) return fail(GGS_EINVAL, "edge scale %d must be >= 1", s);
+        if (H / s < 1 || W / s < 1) return fail(GGS_EINVAL, "edge scale %d leaves no pixel of %dx%d", s, H, W);
+    }
+    if (p->smooth > 0 && p->smooth % 2 == 0)
+        return fail(GGS_EINVAL, "smooth=%d must be odd (an even window changes the array's size)", p->smooth);
+    return GGS_OK;
+}
+
+// ctx locked, device set
+int run_targets_prepare(DevCtx* c, hipStream_t st, const float* d_images, int K, int H0, int W0, int H, int W,
+                        const ggs_mask_params* p, float* d_targets, float* d_masks) {
+    Workspace* w = workspace_for(c, st);
+    int rc;
+    if ((rc = ensure(w->maskws, targets_prepare_ws_bytes(K, H, W, p != nullptr), st))) return rc;
+    GGS_HIP(launch_targets_prepare(st, d_images, K, H0, W0, H, W, p, d_targets, d_masks, w->maskws.p));
+    return GGS_OK;
+}
+}  // namespace
+}  // namespace ggs
+extern "C" {
+
+int ggs_targets_prepare_device(int32_t device, void* stream, const float* d_images, int32_t K, int32_t H0,
+                               int32_t W0, int32_t H, int32_t W, const ggs_mask_params* params,
+                               float* d_targets_khw3, float* d_masks_khw) {
+    int rc = check_prepare(d_images, K, H0, W0, H, W, params, d_targets_khw3, d_masks_khw);
+    if (rc) return rc;
+    DevCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    return run_targets_prepare(c, (hipStream_t)stream, d_images, K, H0, W0, H, W, params, d_targets_khw3,
+                               d_masks_khw);
+}
+
+int ggs_targets_prepare(const float* images, int32_t K, int32_t H0, int32_t W0, int32_t H, int32_t W,
+                        const ggs_mask_params* params, float* targets, float* masks, int32_t device) {
+    int rc = check_prepare(images, K, H0, W0, H, W, params, targets, masks);
+    if (rc) return rc;
+    DevCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    const hipStream_t st = c->stream;
+    const size_t ib = sizeof(float) * 3 * (size_t)K * H0 * W0, tb = sizeof(float) * 3 * (size_t)K * H * W,
+                 mb = sizeof(float) * (size_t)K * H * W;
+    if ((rc = ensure(c->prep_in, ib, st)) || (rc = ensure(c->prep_tgt, tb, st)) ||
+        (params && (rc = ensure(c->prep_mask, mb, st))))
+        return rc;
+    StreamDrain drain;
+    drain.add(c->dev, st);
+    GGS_HIP(hipMemcpyAsync(c->prep_in.p, images, ib, hipMemcpyHostToDevice, st));
+    if ((rc = run_targets_prepare(c, st, (const float*)c->prep_in.p, K, H0, W0, H, W, params, (float*)c->prep_tgt.p,
+                                  params ? (float*)c->prep_mask.p : nullptr)))
+        return rc;
+    GGS_HIP(hipMemcpyAsync(targets, c->prep_tgt.p, tb, hipMemcpyDeviceToHost, st));
+    if (params) GGS_HIP(hipMemcpyAsync(masks, c->prep_mask.p, mb, hipMemcpyDeviceToHost, st));
+    return drain.drain();
+}
+
+int ggs_quantiles(const float* x, int64_t n, const double* q, int32_t nq, float* out) {
+    if (!x || !q || !out) return fail(GGS_EINVAL, "null pointer");
+    if (n < 1 || n >= ((int64_t)1 << 31)) return fail(GGS_EINVAL, "n=%lld must be in 1..2^31-1", (long long)n);
+    if (nq < 1 || nq > kMaxQuantiles) return fail(GGS_EINVAL, "nq=%d must be in 1..%d", nq, kMaxQuantiles);
+    for (int i = 0; i < nq; ++i)
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail(GGS_EINVAL, "q[%d]=%g is outside [0, 1]", i, q[i]);
+    int rc;
+    std::vector<DevCtx*> cs;
+    if ((rc = active_ctxs(1, &cs))) return rc;
+    DevCtx* c = cs[0];
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    const hipStream_t st = c->stream;
+    Workspace* w = workspace_for(c, st);
+    const size_t xb = sizeof(float) * (size_t)n;
+    if ((rc = ensure(c->prep_in, xb, st)) || (rc = ensure(c->prep_mask, sizeof(float) * kMaxQuantiles, st)) ||
+        (rc = ensure(w->maskws, quantile_ws_bytes(1, nq), st)))
+        return rc;
+    StreamDrain drain;
+    drain.add(c->dev, st);
+    GGS_HIP(hipMemcpyAsync(c->prep_in.p, x, xb, hipMemcpyHostToDevice, st));
+    GGS_HIP(launch_quantiles(st, (const float*)c->prep_in.p, 1, n, q, nq, w->maskws.p, (float*)c->prep_mask.p));
+    GGS_HIP(hipMemcpyAsync(out, c->prep_mask.p, sizeof(float) * nq, hipMemcpyDeviceToHost, st));
+    return drain.drain();
 }
 
 int ggs_render_device(int32_t device, void* stream, const float* d_genomes, int64_t B, int32_t N,

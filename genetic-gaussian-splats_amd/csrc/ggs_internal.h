@@ -291,6 +291,21 @@ hipError_t launch_ga_migrate_copy(hipStream_t st, int K, float* pop, const float
 hipError_t launch_ga_migrate_install(hipStream_t st, int K, float* fits, int P, int m, int elite_k, const int* mig,
                                      const float* refit, int* elite);
 
+// ---- target preparation and importance mask (ggs_mask.hip) ---------------------
+// K images [K][H0][W0][3] -> targets [K][H][W][3] (prepare_target) and, with prm,
+// masks [K][H][W] (compute_importance_mask of each prepared target), enqueued on
+// st with no host synchronisation.  ws: targets_prepare_ws_bytes of scratch that
+// stays valid until the work has run.  The arguments are validated by the caller.
+constexpr int kMaxQuantiles = 8;
+size_t targets_prepare_ws_bytes(int K, int H, int W, bool masks);
+hipError_t launch_targets_prepare(hipStream_t st, const float* imgs, int K, int H0, int W0, int H, int W,
+                                  const ggs_mask_params* prm, float* targets, float* masks, void* ws);
+// numpy's 'linear' quantiles q [nq] (host array, nq <= kMaxQuantiles) of each of A
+// arrays of n floats at x + a * n, by exact radix select -> d_out [A][nq] float32.
+size_t quantile_ws_bytes(int A, int nq);
+hipError_t launch_quantiles(hipStream_t st, const float* x, int A, int64_t n, const double* q, int nq, void* ws,
+                            float* d_out);
+
 // ---- RCCL (ggs_comm.cpp) ----------------------------------------------------
 // Grouped in-place all-gather over single-process communicators (ggs_comm_init_local):
 // buf[d] holds shard d at buf[d] + d*per; afterwards every buf[d] holds all n shards.

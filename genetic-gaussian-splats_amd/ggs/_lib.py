@@ -46,6 +46,13 @@ class GaIslands(C.Structure):
                 ("topology", C.c_int32), ("seeds", C.POINTER(C.c_uint64))]
 
 
+class MaskParams(C.Structure):
+    """ggs_mask_params (include/ggs.h)."""
+    _fields_ = [("n_scales", C.c_int32), ("edge_scales", C.c_int32 * 4), ("w_edge", C.c_float),
+                ("w_var", C.c_float), ("gamma", C.c_float), ("floor", C.c_float),
+                ("strength", C.c_float), ("smooth", C.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/ggs.h one-for-one
 SIGNATURES = {
     "ggs_version": (C.c_char_p, []),
@@ -80,6 +87,12 @@ SIGNATURES = {
     "ggs_fitness_device_planset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                              C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "ggs_planset_destroy": (None, [C.c_void_p]),
+    "ggs_targets_prepare_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_int32, C.POINTER(MaskParams),
+                                             C.c_void_p, C.c_void_p]),
+    "ggs_targets_prepare": (C.c_int, [_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(MaskParams), _f32p, _f32p, C.c_int32]),
+    "ggs_quantiles": (C.c_int, [_f32p, C.c_int64, _f64p, C.c_int32, _f32p]),
     "ggs_ga_create": (C.c_int, [C.c_int32, C.POINTER(GaConfig), _f32p, _f32p, _f32p,
                                 C.POINTER(C.c_void_p)]),
     "ggs_ga_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(GaDraws)]),

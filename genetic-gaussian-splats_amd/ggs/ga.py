@@ -558,7 +558,7 @@ def genetic_approx_many(images, H: int, W: int, device, pop_size: int, n_splats:
                         mask_strength: float, boost_only: bool, *, seed: Optional[int] = None,
                         migrate_every: int = 0, migrants: int = 0,
                         init_population: Optional[np.ndarray] = None, chunk: int = 50,
-                        progress: bool = True, return_state: bool = False):
+                        progress: bool = True, return_state: bool = False, prep: str = "host"):
     """``genetic_approx`` (device backend) for K images in one session: an island
     group with a target per island (``ga_device.DeviceGAIslands`` with a 4-D
     target), one breed and one raster launch per generation for all K.
@@ -570,25 +570,34 @@ def genetic_approx_many(images, H: int, W: int, device, pop_size: int, n_splats:
     of ``genetic_approx(images[k], ..., seed=seed + k, backend="device")``, bit for
     bit; with migration the ``migrants`` best of image k - 1's population are
     re-scored against image k before they replace its worst (neighbouring frames
-    or tiles seed each other).
+    or tiles seed each other).  ``prep="device"`` prepares the K targets and masks
+    on the device (``mask.prepare_targets``, within 2e-5 of the host's; the default
+    ``"host"`` keeps every earlier result).
 
     Returns a list of K ``(best individual [N, 9], best fitness)``; with
     ``return_state`` each entry is ``(best, best_fit, {"population", "fitness",
     "curves"})``.  No frames, CSV or PNG outputs."""
     from . import api
     from .ga_device import run_device_ga_islands
-    from .mask import compute_importance_mask, prepare_target
+    from .mask import compute_importance_mask, prepare_target, prepare_targets
 
     images = list(images)
     K = len(images)
     if K < 1:
         raise ValueError("genetic_approx_many needs at least one image")
+    if prep not in ("host", "device"):
+        raise ValueError(f"prep must be 'host' or 'device', got {prep!r}")
     seed = resolve_seed(seed)
     seeds = [(seed + k) % 2**64 for k in range(K)]
-    targets = np.stack([prepare_target(im, H, W) for im in images])
-    masks = np.stack([compute_importance_mask(t, H, W, edge_scales=(1, 2, 4), w_edge=0.7, w_var=0.3,
-                                              gamma=0.7, floor=0.15, smooth=3, strength=mask_strength)
-                      for t in targets])
+    if prep == "device":
+        targets, masks = prepare_targets(images, H, W, edge_scales=(1, 2, 4), w_edge=0.7, w_var=0.3,
+                                         gamma=0.7, floor=0.15, smooth=3, strength=mask_strength,
+                                         backend="device", device=device)
+    else:
+        targets = np.stack([prepare_target(im, H, W) for im in images])
+        masks = np.stack([compute_importance_mask(t, H, W, edge_scales=(1, 2, 4), w_edge=0.7, w_var=0.3,
+                                                  gamma=0.7, floor=0.15, smooth=3, strength=mask_strength)
+                          for t in targets])
     if init_population is not None:
         pops = np.array(init_population, np.float32, copy=True)
         if pops.ndim != 4 or pops.shape[0] != K:

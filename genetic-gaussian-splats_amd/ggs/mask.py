@@ -3,8 +3,11 @@
 Restates modules/mask.py:1-83 (the per-pixel weight of the weighted fitness,
 computed once per run at algorithm.py:42-49 / annealing.py:89-95) and the target
 resize of algorithm.py:33-39 / annealing.py:19-26.  One-shot work off the timed
-path, so it stays on the host; pinned against the reference's own output in
-tests/golden/mask.npz (tests/test_mask.py).
+path for a single image, so these functions stay on the host; pinned against the
+reference's own output in tests/golden/mask.npz (tests/test_mask.py).
+``prepare_targets`` does both for K images at once, on the host (this file's
+functions, image by image) or on the device (csrc/ggs_mask.hip through
+``ggs_targets_prepare``; tests/test_gpu_mask.py).
 """
 from __future__ import annotations
 
@@ -127,3 +130,87 @@ def prepare_target(target_img, H: int, W: int) -> np.ndarray:
     if t.shape[0] != H or t.shape[1] != W:
         t = np.moveaxis(resize_bilinear(np.moveaxis(t, -1, 0), H, W), 0, -1)
     return np.ascontiguousarray(t, np.float32)
+
+
+def mask_params(edge_scales=(1, 2, 4), w_edge: float = 0.7, w_var: float = 0.3, gamma: float = 0.7,
+                floor: float = 0.15, smooth: int = 3, strength: float = 1.0):
+    """A ``ggs_mask_params`` (include/ggs.h) of compute_importance_mask's keyword arguments."""
+    from ._lib import GGSInputError, MaskParams
+    scales = [int(s) for s in edge_scales]
+    if not 1 <= len(scales) <= 4:
+        raise GGSInputError(f"edge_scales must name 1..4 scales, got {len(scales)}")
+    p = MaskParams()
+    p.n_scales = len(scales)
+    for i, s in enumerate(scales):
+        p.edge_scales[i] = s
+    p.w_edge, p.w_var, p.gamma, p.floor, p.strength = w_edge, w_var, gamma, floor, strength
+    p.smooth = int(smooth) if smooth else 0
+    return p
+
+
+def quantiles(x, q) -> np.ndarray:
+    """``ggs_quantiles``: numpy's 'linear' quantiles ``q`` of the flattened float32
+    ``x`` as float32, by the device's exact radix select (what the device _norm01 uses)."""
+    import ctypes as C
+    from . import _lib
+    x = np.ascontiguousarray(x, np.float32).ravel()
+    qa = np.ascontiguousarray(np.atleast_1d(q), np.float64)
+    out = np.empty(qa.size, np.float32)
+    _lib.ensure_init()
+    _lib.check(_lib.lib.ggs_quantiles(x.ctypes.data_as(_lib._f32p), x.size,
+                                      qa.ctypes.data_as(C.POINTER(C.c_double)), qa.size,
+                                      out.ctypes.data_as(_lib._f32p)), "ggs_quantiles")
+    return out
+
+
+def prepare_targets(images, H: int, W: int, *, strength: float, edge_scales=(1, 2, 4),
+                    w_edge: float = 0.7, w_var: float = 0.3, gamma: float = 0.7, floor: float = 0.15,
+                    smooth: int = 3, backend: str = "device", device=None):
+    """``prepare_target`` and ``compute_importance_mask`` for K images at once →
+    ``(targets [K,H,W,3], masks [K,H,W])`` float32.
+
+    ``images``: a [K,H0,W0,3] array or a list of [H0,W0,3] images.  Images of
+    different input sizes are grouped by shape, one library call
+    (``ggs_targets_prepare``) per shape; the outputs keep the input order.
+    ``backend="host"`` is the per-image numpy loop (the same bits as calling the two
+    functions image by image); ``"device"`` runs csrc/ggs_mask.hip on ``device``."""
+    H, W = int(H), int(W)
+    if backend not in ("host", "device"):
+        raise ValueError(f"backend must be 'host' or 'device', got {backend!r}")
+    imgs = [np.asarray(im) for im in images]
+    K = len(imgs)
+    if K < 1:
+        raise ValueError("prepare_targets needs at least one image")
+    for im in imgs:
+        if im.ndim != 3 or im.shape[2] != 3:
+            raise ValueError(f"an image must be [H0,W0,3], got {tuple(im.shape)}")
+    kw = dict(edge_scales=tuple(edge_scales), w_edge=w_edge, w_var=w_var, gamma=gamma, floor=floor,
+              smooth=smooth, strength=strength)
+    if backend == "host":
+        targets = np.stack([prepare_target(im, H, W) for im in imgs])
+        masks = np.stack([compute_importance_mask(t, H, W, **kw) for t in targets])
+        return targets, masks
+    from . import _lib, api
+    prm = mask_params(**kw)
+    dev = api.device_index(device)
+    targets = np.empty((K, H, W, 3), np.float32)
+    masks = np.empty((K, H, W), np.float32)
+    for shape, idx in group_by_shape(imgs):
+        batch = np.ascontiguousarray(np.stack([imgs[i] for i in idx]), np.float32)
+        t = np.empty((len(idx), H, W, 3), np.float32)
+        m = np.empty((len(idx), H, W), np.float32)
+        # the C layer validates first (GGS_EINVAL before any device is touched)
+        _lib.check(_lib.lib.ggs_targets_prepare(batch.ctypes.data_as(_lib._f32p), len(idx), shape[0], shape[1],
+                                                H, W, prm, t.ctypes.data_as(_lib._f32p),
+                                                m.ctypes.data_as(_lib._f32p), dev), "ggs_targets_prepare")
+        targets[idx] = t
+        masks[idx] = m
+    return targets, masks
+
+
+def group_by_shape(imgs):
+    """[((H0, W0), [indices in input order]), ...] in order of first appearance."""
+    groups = {}
+    for i, im in enumerate(imgs):
+        groups.setdefault((int(im.shape[0]), int(im.shape[1])), []).append(i)
+    return list(groups.items())

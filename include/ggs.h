@@ -140,6 +140,54 @@ int ggs_fitness_device_planset(void* planset, void* stream, const float* d_genom
                                int32_t N, int32_t C, int32_t group, float k_sigma, float* d_out_B);
 void ggs_planset_destroy(void* planset);
 
+/* ---- target preparation and importance mask (K images at once) ---------------
+ * The inputs of the weighted fitness, made on the device from K images of one
+ * size: targets [K,H,W,3] as algorithm.py:33-39 prepares them (float32, /255
+ * when the image's maximum is > 1.5, bilinear resize to (H, W), align_corners
+ * False; the identity when the sizes match) and masks [K,H,W] as
+ * modules/mask.py:29-83 computes them from each prepared target (the range rule
+ * once more on the prepared target, as the reference applies it; luma;
+ * multi-scale Sobel edges; 9x9 local variance; _norm01 with exact 2 % / 98 %
+ * quantiles; optional smoothing; gamma, floor and strength).  Every launch covers
+ * all K images; image k's result has the bits a K = 1 call gives it, and two runs
+ * agree bit for bit (integer atomics only).
+ *
+ * The outputs are what ggs_planset_create (d_targets_khw3, d_masks_khw) and, for
+ * K = 1, ggs_plan_create (d_target_hw3, d_mask_hw) take: prepare on a stream,
+ * create the plan or plan set on the same stream, and no host code touches the
+ * pixels in between.
+ *
+ * params: edge_scales[0..n_scales) are summed in the order given (1 <= n_scales
+ * <= 4, each scale s >= 1 with H / s >= 1 and W / s >= 1); smooth <= 0: no
+ * smoothing, otherwise an odd window (an even one changes the array's size in
+ * the reference); the reference's defaults are scales 1, 2, 4, w_edge 0.7, w_var
+ * 0.3, gamma 0.7, floor 0.15, smooth 3 (algorithm.py:42-49).  params == NULL:
+ * targets only, and d_masks_khw must be NULL.
+ * Reported as GGS_EINVAL before any device is touched: K < 1 (or > 65535), null
+ * pointers, sizes < 1, min(H, W) < 4 and the parameter rules above. */
+typedef struct ggs_mask_params {
+    int32_t n_scales;
+    int32_t edge_scales[4];
+    float w_edge, w_var, gamma, floor, strength;
+    int32_t smooth;
+} ggs_mask_params;
+
+/* Device form: d_images [K,H0,W0,3], d_targets_khw3 and d_masks_khw are device
+ * pointers on `device`; the work is enqueued on `stream` (scratch comes from the
+ * library's pooled per-stream workspace) and the call returns without
+ * synchronising. */
+int ggs_targets_prepare_device(int32_t device, void* stream, const float* d_images, int32_t K, int32_t H0,
+                               int32_t W0, int32_t H, int32_t W, const ggs_mask_params* params,
+                               float* d_targets_khw3, float* d_masks_khw);
+/* Host-pointer form (synchronous) on HIP device `device`. */
+int ggs_targets_prepare(const float* images, int32_t K, int32_t H0, int32_t W0, int32_t H, int32_t W,
+                        const ggs_mask_params* params, float* targets, float* masks, int32_t device);
+/* Stage export (host pointers; parity tests): out[i] = numpy's 'linear' quantile
+ * q[i] of x[0..n), float32 of the double interpolation between the two order
+ * statistics around q[i] (n - 1), found by the radix select _norm01 uses.
+ * 1 <= n < 2^31, 1 <= nq <= 8, 0 <= q[i] <= 1; -0 counts as +0, no NaNs. */
+int ggs_quantiles(const float* x, int64_t n, const double* q, int32_t nq, float* out);
+
 /* ---- device-resident GA ------------------------------
  * genetic_approx's generation loop (algorithm.py:85-155) on one device: the
  * population, fitness, elites, best individual and curves stay in HBM; a
