@@ -2336,6 +2336,57 @@ int ggs_sa_accept_uniform(uint64_t seed, int32_t it, int32_t k, double* u) {
     return GGS_OK;
 }
 
+int ggs_ga_philox_draws(int32_t device, uint64_t seed, int32_t gen, int32_t first, int32_t n_off, int32_t P,
+                        int32_t N, int32_t tour_k, float cxpb, const ggs_ga_draws_out* out) {
+    if (n_off < 1 || P < 1 || N < 1 || tour_k < 1)
+        return fail(GGS_EINVAL, "n_off=%d, P=%d, N=%d, tour_k=%d must be >= 1", n_off, P, N, tour_k);
+    if (gen < 0 || first < 0) return fail(GGS_EINVAL, "gen=%d, first=%d must be >= 0", gen, first);
+    const int64_t on = (int64_t)n_off * N, np2 = (n_off + 1) / 2;
+    if (on > ((int64_t)1 << 27) || (int64_t)P * tour_k > ((int64_t)1 << 27))
+        return fail(GGS_EINVAL, "n_off*N=%lld, P*tour_k=%lld exceed the limit of 2^27 draws per array",
+                    (long long)on, (long long)P * tour_k);
+    if (!out) return fail(GGS_EINVAL, "null output");
+    GaDrawsOut d{};
+    struct Seg { void* host; int64_t bytes; void** dev; };
+    Seg segs[] = {
+        {out->tour_idx, 4 * (int64_t)P * tour_k, (void**)&d.tour_idx}, {out->perm, 4 * (int64_t)P, (void**)&d.perm},
+        {out->cx, 4 * np2, (void**)&d.cx}, {out->cx_u, 4 * np2 * N, (void**)&d.cx_u},
+        {out->u_xy, 8 * on, (void**)&d.u_xy}, {out->u_ab, 8 * on, (void**)&d.u_ab},
+        {out->u_t, 4 * on, (void**)&d.u_t}, {out->u_rgb, 4 * on, (void**)&d.u_rgb},
+        {out->u_a, 4 * on, (void**)&d.u_a}, {out->k_color, 4 * (int64_t)n_off, (void**)&d.k_color},
+        {out->k_xy, 4 * (int64_t)n_off, (void**)&d.k_xy}, {out->k_ab, 4 * (int64_t)n_off, (void**)&d.k_ab},
+        {out->k_t, 4 * (int64_t)n_off, (void**)&d.k_t}, {out->n_xy, 8 * on, (void**)&d.n_xy},
+        {out->n_ab, 8 * on, (void**)&d.n_ab}, {out->n_t, 4 * on, (void**)&d.n_t},
+        {out->n_rgba, 16 * on, (void**)&d.n_rgba}, {out->swap_i, 4 * (int64_t)n_off, (void**)&d.swap_i},
+        {out->swap_pick, 4 * (int64_t)n_off, (void**)&d.swap_pick},
+        {out->swap_u, 8 * (int64_t)n_off, (void**)&d.swap_u},
+    };
+    int64_t total = 0;
+    for (const Seg& g : segs) {
+        if (!g.host) return fail(GGS_EINVAL, "null output: every draws array is required");
+        total += (g.bytes + 255) & ~(int64_t)255;
+    }
+    int rc;
+    DevCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    struct Scratch {
+        void* p = nullptr;
+        ~Scratch() { if (p) (void)hipFree(p); }
+    } buf;
+    GGS_HIP(hipMalloc(&buf.p, (size_t)total));
+    char* base = (char*)buf.p;
+    for (const Seg& g : segs) {
+        *g.dev = base;
+        base += (g.bytes + 255) & ~(int64_t)255;
+    }
+    GGS_HIP(launch_ga_philox_draws(c->stream, seed, gen, first, n_off, P, N, tour_k, cxpb, d));
+    GGS_HIP(hipStreamSynchronize(c->stream));
+    for (const Seg& g : segs) GGS_HIP(hipMemcpy(g.host, *g.dev, (size_t)g.bytes, hipMemcpyDeviceToHost));
+    return GGS_OK;
+}
+
 int ggs_sa_set_incremental(void* handle, int32_t on) {
     if (!handle) return fail(GGS_EINVAL, "null handle");
     SaSession* s = (SaSession*)handle;

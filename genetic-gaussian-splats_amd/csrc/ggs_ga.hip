@@ -1466,4 +1466,68 @@ hipError_t launch_sa_accept(hipStream_t st, SaLoopDev* sl, const SaItDev* sit, c
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// stage export (ggs_ga_philox_draws): the Philox-mode draws as explicit arrays
+// ---------------------------------------------------------------------------
+// What the variation kernels draw in Philox mode for generation `gen` (SA:
+// iteration), offspring first .. first+n_off-1 (SA: tries), written in the
+// explicit-draw layout (GaDrawsDev), every slot filled whether or not a kernel
+// would consume it.  The per-splat and per-offspring draws come from the helpers
+// the kernels call (mask_draws, normal_draws, fallbacks with no flag set, u01,
+// rng.block); the expressions ga_variation_body writes inline (crossover
+// decision and mask uniform, tournament index, swap_i, swap_u) are restated.
+// `first` moves only the offspring identity og (S_MASK, S_NORM_*, S_IND): pairs
+// and tournament slots are counted from the launch's offspring 0, as the
+// kernels count them.  One thread per output element of the largest array.
+__global__ void __launch_bounds__(256)
+ga_philox_draws_kernel(uint32_t k0, uint32_t k1, int gen, int first, int n_off, int P, int N, int tour_k, float cxpb,
+                       GaDrawsOut out) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const Rng rng{k0, k1, (uint32_t)gen};
+    const GaDrawsDev d{};
+    const int npairs = (n_off + 1) / 2;
+    if (t < (int64_t)n_off * N) {              // per offspring and splat: mask uniforms, normals
+        const int o = (int)(t / N), s = (int)(t % N);
+        const uint32_t og = (uint32_t)(o + first);
+        const MaskU u = mask_draws(d, rng, og, 0, s);
+        const NormD n = normal_draws(d, rng, og, 0, s, N);
+        out.u_xy[t * 2] = u.ux0; out.u_xy[t * 2 + 1] = u.ux1;
+        out.u_ab[t * 2] = u.ua0; out.u_ab[t * 2 + 1] = u.ua1;
+        out.u_t[t] = u.ut; out.u_rgb[t] = u.urgb; out.u_a[t] = u.ua;
+        out.n_xy[t * 2] = n.nx0; out.n_xy[t * 2 + 1] = n.nx1;
+        out.n_ab[t * 2] = n.na0; out.n_ab[t * 2 + 1] = n.na1;
+        out.n_t[t] = n.nt;
+        out.n_rgba[t * 4] = n.nr0; out.n_rgba[t * 4 + 1] = n.nr1;
+        out.n_rgba[t * 4 + 2] = n.nr2; out.n_rgba[t * 4 + 3] = n.nr3;
+    }
+    if (t < (int64_t)npairs * N) {             // crossover mask uniform of (pair, splat), shared by the pair
+        const int pair = (int)(t / N), s = (int)(t % N);
+        out.cx_u[t] = u01(rng.block(S_CX, (uint32_t)pair, (uint32_t)(s + 1)).x);
+    }
+    if (t < (int64_t)P * tour_k) {             // candidate j of tournament slot q
+        const int q = (int)(t / tour_k), j = (int)(t % tour_k);
+        out.tour_idx[t] = min((int)(u01(rng.block(S_TOUR, (uint32_t)q, (uint32_t)j).x) * (float)P), P - 1);
+    }
+    if (t < P) out.perm[t] = (int)t;           // Philox mode does not shuffle
+    if (t < npairs) out.cx[t] = u01(rng.block(S_CX, (uint32_t)t, 0).x) < cxpb;
+    if (t < n_off) {                           // per offspring: fallbacks, swap
+        const int o = (int)t;
+        const uint32_t og = (uint32_t)(o + first);
+        const Fallback f = fallbacks(d, rng, og, o, N, 0);
+        out.k_color[o] = f.kc; out.k_xy[o] = f.kx; out.k_ab[o] = f.kb; out.k_t[o] = f.kt;
+        out.swap_i[o] = N >= 2 ? (int)(rng.block(S_IND, og, 4).x % (uint32_t)(N - 1)) : 0;
+        out.swap_pick[o] = -1;
+        out.swap_u[o] = (double)u01(rng.block(S_IND, og, 5).x);
+    }
+}
+
+hipError_t launch_ga_philox_draws(hipStream_t st, uint64_t seed, int gen, int first, int n_off, int P, int N,
+                                  int tour_k, float cxpb, const GaDrawsOut& out) {
+    // the largest array: [n_off*N] (>= npairs*N, n_off, npairs) or [P*tour_k] (>= P)
+    const int64_t a = (int64_t)n_off * N, b = (int64_t)P * tour_k, n = a > b ? a : b;
+    hipLaunchKernelGGL(ga_philox_draws_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), gen, first, n_off, P, N, tour_k, cxpb, out);
+    return hipGetLastError();
+}
+
 }  // namespace ggs

@@ -132,6 +132,25 @@ struct GaDrawsDev {             // explicit draws (device pointers); all NULL ->
     const int *swap_i, *swap_pick;    // [P]
     const double* swap_u;       // [P]
 };
+struct GaDrawsOut {             // GaDrawsDev's mutable twin (device pointers): the stage export's outputs
+    int* tour_idx;              // [P*k]
+    int* perm;                  // [P]
+    int* cx;                    // [npairs], npairs = ceil(n_off / 2)
+    float* cx_u;                // [npairs*N]
+    float *u_xy, *u_ab;         // [n_off*N*2]
+    float *u_t, *u_rgb, *u_a;   // [n_off*N]
+    int *k_color, *k_xy, *k_ab, *k_t;   // [n_off]
+    float *n_xy, *n_ab;         // [n_off*N*2]
+    float* n_t;                 // [n_off*N]
+    float* n_rgba;              // [n_off*N*4]
+    int *swap_i, *swap_pick;    // [n_off]
+    double* swap_u;             // [n_off]
+};
+// The draws the variation kernels take in Philox mode for generation `gen` (SA:
+// iteration), offspring first .. first+n_off-1 (SA: tries), as explicit arrays
+// (ggs_ga_philox_draws; one small kernel built from the kernels' own draw helpers).
+hipError_t launch_ga_philox_draws(hipStream_t st, uint64_t seed, int gen, int first, int n_off, int P, int N,
+                                  int tour_k, float cxpb, const GaDrawsOut& out);
 struct GaBestDev {
     double* fit;
     int* src;

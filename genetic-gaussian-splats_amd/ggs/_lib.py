@@ -122,6 +122,9 @@ SIGNATURES = {
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint64)]),
     "ggs_sa_accept_uniform": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
+    # ggs_ga_draws_out is ggs_ga_draws with writable arrays: one ctypes structure serves both
+    "ggs_ga_philox_draws": (C.c_int, [C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_float, C.POINTER(GaDraws)]),
     "ggs_comm_unique_id": (C.c_int, [C.c_void_p]),
     "ggs_comm_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                   C.POINTER(C.c_void_p)]),

@@ -332,6 +332,34 @@ def draws_from_host(tour_idx, perm, cx, cxu_compact, mut, N: int) -> Dict[str, n
     return out
 
 
+def philox_draws(seed: int, gen: int, n_off: int, P: int, N: int, tour_k: int, cxpb: float,
+                 first: int = 0, device: int = 0) -> Dict[str, np.ndarray]:
+    """ggs_ga_philox_draws (a stage export for parity tests): the draws the
+    variation kernels take from the in-kernel Philox stream keyed by ``seed`` for
+    generation ``gen`` (SA: iteration) and offspring ``first .. first+n_off-1``
+    (SA: tries), computed on the device by the kernels' own draw functions, as the
+    dict ``DeviceGA.step`` / ``DeviceSA.propose`` accept (ggs/ga.py's shapes, the
+    crossover masks one row per pair).  A Philox run is the explicit run on these
+    draws: ``DeviceGA(seed=s).run(g, 1, G)`` equals ``step(g, G, philox_draws(s, g,
+    P, P, N, tour_k, cxpb))``, and ``propose(it, total, first_try, n)`` equals
+    ``propose(..., draws=philox_draws(s, it, n, n, N, 1, 0.0, first=first_try))``."""
+    n, np2 = int(n_off), (int(n_off) + 1) // 2
+    shapes = {"tour_idx": (P, tour_k), "perm": (P,), "cx": (np2,), "cx_u": (np2, N),
+              "u_xy": (n, N, 2), "u_ab": (n, N, 2), "u_t": (n, N, 1), "u_rgb": (n, N, 1), "u_a": (n, N, 1),
+              "k_color": (n,), "k_xy": (n,), "k_ab": (n,), "k_t": (n,),
+              "n_xy": (n, N, 2), "n_ab": (n, N, 2), "n_t": (n, N, 1), "n_rgba": (n, N, 4),
+              "swap_i": (n,), "swap_pick": (n,), "swap_u": (n,)}
+    out, d = {}, GaDraws()
+    for name, typ in GaDraws._fields_:
+        dt = np.float64 if name == "swap_u" else (np.int32 if typ is _i32p else np.float32)
+        out[name] = np.empty([max(int(v), 0) for v in shapes[name]], dt)
+        setattr(d, name, out[name].ctypes.data_as(typ))
+    # arguments are validated before the library looks for a device
+    check(lib.ggs_ga_philox_draws(int(device), int(seed) & (2**64 - 1), int(gen), int(first), n, int(P),
+                                  int(N), int(tour_k), float(cxpb), C.byref(d)), "ggs_ga_philox_draws")
+    return out
+
+
 class RecordingDraws:
     """Wraps a ggs.ga draw source and keeps, per generation, the draws
     ``next_generation`` consumed — in the device layout (``draws_from_host``)."""

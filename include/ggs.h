@@ -346,6 +346,33 @@ int ggs_sa_loop_state(void* handle, double* best_fit, double* curr_fit, uint64_t
 /* The acceptance uniform in [0, 1) ggs_sa_run draws for try k of iteration it
  * (lets a host loop reproduce the device loop's trajectory). */
 int ggs_sa_accept_uniform(uint64_t seed, int32_t it, int32_t k, double* u);
+/* Stage export (host pointers; parity tests): the draws the GA / SA variation
+ * kernels take from their in-kernel Philox4x32-10 stream (counter (gen, who,
+ * what, stream), key = seed; DESIGN.md has the layout) for generation `gen`
+ * (SA: iteration `it`) and offspring first .. first+n_off-1 (SA: tries; `first`
+ * is ggs_sa_propose's first_try, 0 for the GA), computed on `device` by the
+ * kernels' own draw functions and written into caller-owned host arrays in the
+ * ggs_ga_draws layout: per-offspring arrays are indexed by the local offspring
+ * 0 .. n_off-1 ([n_off*N*2] ..., [n_off]), cx / cx_u by the local pair
+ * ([ceil(n_off/2)], [ceil(n_off/2)*N]), tour_idx [P*tour_k] and perm [P] by the
+ * tournament slot.  Every slot is filled, also those a kernel would not consume
+ * (a fallback index when a mask flag is set, ...).  Philox mode's conventions:
+ * perm is the identity, cx = (u01 < cxpb), swap_pick = -1 with swap_u the
+ * uniform, swap_i = 0 when N < 2.  ggs_ga_step / ggs_sa_propose fed these
+ * arrays compute what the Philox run computes, bit for bit.
+ * n_off, P, N, tour_k < 1, gen or first < 0, a null array and sizes past 2^27
+ * draws per array are reported (GGS_EINVAL) before any device is touched. */
+typedef struct ggs_ga_draws_out {     /* ggs_ga_draws with writable arrays, same order */
+    int32_t *tour_idx, *perm, *cx;
+    float* cx_u;
+    float *u_xy, *u_ab, *u_t, *u_rgb, *u_a;
+    int32_t *k_color, *k_xy, *k_ab, *k_t;
+    float *n_xy, *n_ab, *n_t, *n_rgba;
+    int32_t *swap_i, *swap_pick;
+    double* swap_u;
+} ggs_ga_draws_out;
+int ggs_ga_philox_draws(int32_t device, uint64_t seed, int32_t gen, int32_t first, int32_t n_off, int32_t P,
+                        int32_t N, int32_t tour_k, float cxpb, const ggs_ga_draws_out* out);
 /* Incremental evaluation (default off): a neighbour's 16-column strips that no
  * changed splat touches (old or new AABB) keep the current state's partial sums —
  * bit-identical to a full re-render; off = every strip is rasterised.  Turning

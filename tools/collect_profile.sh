@@ -26,7 +26,8 @@ with open(sys.argv[2], "w", newline="") as f:
                     int(r["End_Timestamp"]) - int(r["Start_Timestamp"])])
 PY
 done
-sed "s#$SRC/##g" "$SRC/commands.txt" > "$DST/commands.txt"   # output paths relative to the scratch folder
+# output paths relative to the scratch folder (a packed profile still names the folder it was taken in)
+sed -e "s#$SRC/##g" -e "s#${SRC%/*}/prof_$TAG/##g" "$SRC/commands.txt" > "$DST/commands.txt"
 # stamp the git revision: only when this tree's libggs.so is the profiled build
 python3 - "$SRC/summary.json" "$DST/summary.json" <<'PY'
 import hashlib, json, subprocess, sys
