@@ -2444,3 +2444,399 @@ void ggs_sa_destroy(void* handle) {
 }
 
 }  // extern "C"
+
+// ---- SA chain groups -------------------------------------------------------------
+namespace ggs {
+namespace {
+
+struct SaChains {
+    DevCtx* c = nullptr;
+    hipStream_t st = nullptr;
+    ggs_ga_config cfg{};
+    int K = 0, N = 0, cap = 0, nTiles = 0, exchange_every = 0;
+    bool multi = false;             // a target (plan) per chain
+    uint64_t exchange_seed = 0;
+    int64_t gstride = 0;            // floats between the chains' genomes in curr / best
+    DevBuf curr, best, nb, nb_fits, target, mask, nb_recs, nb_bnds, nb_part, plan, wpart, order, fctr;
+    DevBuf loop, sit, curves, flags, sizes, seeds, list, swaps;
+    SaLoopDev* h_loop = nullptr;    // pinned [K]
+    float* h_fits = nullptr;        // pinned [K]
+    unsigned long long* h_swaps = nullptr;   // pinned [2]: exchange pairs tried / swapped
+};
+
+void sc_free(SaChains* s) {
+    for (DevBuf* b : {&s->curr, &s->best, &s->nb, &s->nb_fits, &s->target, &s->mask, &s->nb_recs, &s->nb_bnds,
+                      &s->nb_part, &s->plan, &s->wpart, &s->order, &s->fctr, &s->loop, &s->sit, &s->curves, &s->flags,
+                      &s->sizes, &s->seeds, &s->list, &s->swaps})
+        if (b->p) (void)hipFree(b->p);
+    if (s->h_loop) (void)hipHostFree(s->h_loop);
+    if (s->h_fits) (void)hipHostFree(s->h_fits);
+    if (s->h_swaps) (void)hipHostFree(s->h_swaps);
+    if (s->st) (void)hipStreamDestroy(s->st);
+}
+
+SaChainsDev sc_dev(const SaChains* s, int n_its, int n_tries) {
+    SaChainsDev g{};
+    g.K = s->K;
+    g.n_its = n_its;
+    g.n_tries = n_tries;
+    g.cap = s->cap;
+    g.gstride = s->gstride;
+    g.wstride = s->multi ? (int64_t)(plan_wsum_bytes(s->cfg.H, s->cfg.W) / sizeof(float)) : 0;
+    g.seeds = (const uint64_t*)s->seeds.p;
+    int* l = (int*)s->list.p;       // total (+ 3 of padding), base [K], chain [K * cap], slot [K * cap]
+    g.total = l;
+    g.base = l + 4;
+    g.chain = g.base + s->K;
+    g.slot = g.chain + (size_t)s->K * s->cap;
+    return g;
+}
+
+int sc_check(const ggs_ga_config* cfg, const ggs_sa_chains* ch, const float* target, const float* mask,
+             const float* init_inds, void** handle, bool multi) {
+    if (!cfg || !ch || !target || !init_inds || !handle) return fail(GGS_EINVAL, "null argument");
+    int rc = ga_check_config(*cfg, mask, true);
+    if (rc) return rc;
+    if (ch->n_chains < 1 || ch->n_chains > GGS_SA_MAX_CHAINS)
+        return fail(GGS_EINVAL, "n_chains must be in [1, %d], got %d", GGS_SA_MAX_CHAINS, ch->n_chains);
+    if (!ch->seeds) return fail(GGS_EINVAL, "seeds is required ([n_chains])");
+    if (ch->exchange_every < 0) return fail(GGS_EINVAL, "exchange_every must be >= 0, got %d", ch->exchange_every);
+    if (multi && ch->exchange_every > 0)
+        return fail(GGS_EINVAL, "replica exchange needs one shared target: an energy measured on another image "
+                                "means nothing (exchange_every=%d)", ch->exchange_every);
+    return check_dims((int64_t)ch->n_chains * cfg->pop_size, cfg->n_splats, 9, cfg->H, cfg->W);
+}
+
+int sc_create(int32_t device, const ggs_ga_config* cfg, const ggs_sa_chains* ch, const float* target,
+              const float* mask, const float* init_inds, void** handle, float* init_fits, bool multi) {
+    int rc = sc_check(cfg, ch, target, mask, init_inds, handle, multi);   // before any device call
+    if (rc) return rc;
+    const ggs_ga_config& c = *cfg;
+    DevCtx* ctx = nullptr;
+    if ((rc = get_ctx(device, &ctx))) return rc;
+    auto s = std::make_unique<SaChains>();
+    s->c = ctx;
+    s->cfg = c;
+    ga_fill_log_bounds(&s->cfg);
+    const int K = s->K = ch->n_chains, N = s->N = c.n_splats;
+    s->cap = c.pop_size;
+    s->multi = multi;
+    s->exchange_every = ch->exchange_every;
+    s->exchange_seed = ch->exchange_seed;
+    const size_t n9 = 9 * (size_t)N;
+    s->gstride = (int64_t)((n9 + 3) & ~(size_t)3);
+    const size_t nplans = multi ? (size_t)K : 1, hw = nplans * (size_t)c.H * c.W;
+    const size_t B = (size_t)K * s->cap, BN = B * (size_t)std::max(N, 1);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard dg(ctx->dev);
+    auto bail = [&](int code) {
+        const std::string keep = t_err;
+        if (s->st) (void)hipStreamSynchronize(s->st);
+        sc_free(s.get());
+        t_err = keep;
+        return code;
+    };
+    if (hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess)
+        return bail(fail(GGS_EHIP, "stream creation failed"));
+    int nTX;
+    s->nTiles = raster_tiles(c.H, c.W, &nTX);
+    const size_t slots = 4 * (size_t)s->nTiles, gb = sizeof(float) * std::max<size_t>((size_t)s->gstride * K, 4);
+    if ((rc = ensure(s->curr, gb, s->st)) || (rc = ensure(s->best, gb, s->st)) ||
+        (rc = ensure(s->nb, sizeof(float) * std::max<size_t>(n9 * B, 4), s->st)) ||
+        (rc = ensure(s->nb_fits, sizeof(float) * B, s->st)) ||
+        (rc = ensure(s->target, sizeof(float) * 3 * hw, s->st)) ||
+        (mask && (rc = ensure(s->mask, sizeof(float) * hw, s->st))) ||
+        (rc = ensure(s->nb_recs, sizeof(SplatRec) * BN, s->st)) || (rc = ensure(s->nb_bnds, sizeof(int4) * BN, s->st)) ||
+        (rc = ensure(s->nb_part, sizeof(float) * slots * B, s->st)) ||
+        (rc = ensure(s->plan, nplans * plan_bytes(c.H, c.W), s->st)) ||
+        (rc = ensure(s->wpart, nplans * plan_wsum_bytes(c.H, c.W), s->st)) ||
+        (rc = ensure(s->order, sizeof(int) * (size_t)raster_order_len(c.H, c.W), s->st)) ||
+        (rc = ensure(s->loop, sizeof(SaLoopDev) * K, s->st)) || (rc = ensure(s->sizes, sizeof(float) * BN, s->st)) ||
+        (rc = ensure(s->seeds, sizeof(uint64_t) * K, s->st)) ||
+        (rc = ensure_zeroed(s->list, sizeof(int) * (4 + (size_t)K + 2 * B), s->st)) ||
+        (rc = ensure_zeroed(s->swaps, sizeof(unsigned long long) * 2, s->st)))
+        return bail(rc);
+    if (hipHostMalloc((void**)&s->h_fits, sizeof(float) * K, hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void**)&s->h_swaps, sizeof(unsigned long long) * 2, hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void**)&s->h_loop, sizeof(SaLoopDev) * K, hipHostMallocDefault) != hipSuccess)
+        return bail(fail(GGS_ENOMEM, "pinned allocation failed"));
+    s->h_swaps[0] = s->h_swaps[1] = 0;
+    std::vector<int> order(raster_order_len(c.H, c.W));
+    raster_tile_order(c.H, c.W, order.data());
+    // the K initial individuals, contiguous in the neighbour buffer for their one evaluation
+    if (hipMemcpyAsync(s->target.p, target, sizeof(float) * 3 * hw, hipMemcpyHostToDevice, s->st) ||
+        (mask && hipMemcpyAsync(s->mask.p, mask, sizeof(float) * hw, hipMemcpyHostToDevice, s->st)) ||
+        hipMemcpyAsync(s->nb.p, init_inds, sizeof(float) * n9 * K, hipMemcpyHostToDevice, s->st) ||
+        hipMemcpyAsync(s->seeds.p, ch->seeds, sizeof(uint64_t) * K, hipMemcpyHostToDevice, s->st) ||
+        hipMemcpyAsync(s->order.p, order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice, s->st))
+        return bail(fail(GGS_EHIP, "upload failed"));
+    for (int k = 0; k < K && n9; ++k)
+        if (hipMemcpyAsync((float*)s->curr.p + k * s->gstride, init_inds + n9 * k, sizeof(float) * n9,
+                           hipMemcpyHostToDevice, s->st) ||
+            hipMemcpyAsync((float*)s->best.p + k * s->gstride, init_inds + n9 * k, sizeof(float) * n9,
+                           hipMemcpyHostToDevice, s->st))
+            return bail(fail(GGS_EHIP, "upload failed"));
+    if (launch_plan_set(s->st, (const float*)s->target.p, mask ? (const float*)s->mask.p : nullptr, c.fitness_mode,
+                        c.boost_beta, c.H, c.W, (int)nplans, (float4*)s->plan.p, (float*)s->wpart.p) != hipSuccess)
+        return bail(fail(GGS_EHIP, "plan launch failed"));
+    // one prep and one raster launch for the K initial energies (chain k against
+    // plan k of a plan set: group 1); unfused, as ggs_sa_create evaluates its one
+    if (launch_prep(s->st, true, (const float*)s->nb.p, (int64_t)K * N, 9, c.H, c.W, c.k_sigma, (SplatRec*)s->nb_recs.p,
+                    (int4*)s->nb_bnds.p, nullptr, nullptr, nullptr) != hipSuccess)
+        return bail(fail(GGS_EHIP, "prep launch failed"));
+    if ((rc = raster_fitness(s->st, ctx->simds, (const SplatRec*)s->nb_recs.p, (const int4*)s->nb_bnds.p, K, N, c.H, c.W,
+                             (const float4*)s->plan.p, (float*)s->nb_part.p, (const float*)s->wpart.p, c.fitness_mode,
+                             (const int*)s->order.p, s->fctr, (float*)s->nb_fits.p, false, nullptr, nullptr,
+                             multi ? 1 : 0)))
+        return bail(rc);
+    if (hipMemcpyAsync(s->h_fits, s->nb_fits.p, sizeof(float) * K, hipMemcpyDeviceToHost, s->st) ||
+        hipStreamSynchronize(s->st))
+        return bail(fail(GGS_EHIP, "initial evaluation failed"));
+    for (int k = 0; k < K; ++k) {
+        if (init_fits) init_fits[k] = s->h_fits[k];
+        s->h_loop[k] = SaLoopDev{};
+        s->h_loop[k].acc_j = -1;
+        s->h_loop[k].curr_fit = s->h_loop[k].best_fit = (double)s->h_fits[k];
+    }
+    if (hipMemcpy(s->loop.p, s->h_loop, sizeof(SaLoopDev) * K, hipMemcpyHostToDevice) != hipSuccess)
+        return bail(fail(GGS_EHIP, "upload failed"));
+    *handle = s.release();
+    return GGS_OK;
+}
+
+// One chunk of iterations [first_it, first_it + n) for every chain, no exchange
+// inside it.  temps[k * tstride + i], curves_out[(k * tstride + i) * 2 + {0, 1}].
+int sc_run_chunk(SaChains* s, int first_it, int n, int total_iters, int tries, const double* temps, int tstride,
+                 int width, double* curves_out) {
+    const ggs_ga_config& c = s->cfg;
+    const int K = s->K;
+    std::vector<SaItDev> tab((size_t)K * n);
+    for (int i = 0; i < n; ++i) {
+        const GaParamsDev q = ga_params(c, first_it + i, total_iters);
+        for (int k = 0; k < K; ++k)
+            tab[(size_t)k * n + i] = SaItDev{{q.sig_xy, q.sig_alog, q.sig_blog, q.sig_theta, q.sig_rgb, q.sig_alpha},
+                                             {0.f, 0.f}, temps[(size_t)k * tstride + i]};
+    }
+    const int64_t pos0 = (int64_t)first_it * tries, end = pos0 + (int64_t)n * tries;
+    const int n_tries = (int)(end - pos0);
+    int rc;
+    if ((rc = ensure(s->sit, sizeof(SaItDev) * tab.size(), s->st)) ||
+        (rc = ensure(s->curves, sizeof(double) * 2 * tab.size(), s->st)) ||
+        (rc = ensure(s->flags, sizeof(int) * (size_t)n_tries * K, s->st)))
+        return rc;
+    const SaChainsDev g = sc_dev(s, n, n_tries);
+    SaLoopDev* loop = (SaLoopDev*)s->loop.p;
+    const SaItDev* sit = (const SaItDev*)s->sit.p;
+    GGS_HIP(hipMemcpyAsync(s->sit.p, tab.data(), sizeof(SaItDev) * tab.size(), hipMemcpyHostToDevice, s->st));
+    // Adaptive width for the group: the lone session's rule with the
+    // round's fixed cost (ggs_sa_run's width_r, in neighbour evaluations) divided
+    // by the number of unfinished chains, which share that round, at the mean
+    // acceptance rate of those chains.  One width per batch for all chains.
+    static const double wave_slots = [] {
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) == hipSuccess)
+            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        return 12.0 * (double)cus;
+    }();
+    const double width_r = std::max(0.25, 0.5 * wave_slots / (double)(4 * s->nTiles));
+    bool fresh = true;              // before the chunk's first sync: every chain is unfinished
+    auto unfinished = [&](int k) { return fresh || s->h_loop[k].pos < end; };
+    auto batch_width = [&]() {
+        if (width > 0) return std::min(s->cap, width);
+        double p = 0.0;
+        int u = 0;
+        for (int k = 0; k < K; ++k)
+            if (unfinished(k)) { p += s->h_loop[k].acc_rate; ++u; }
+        u = std::max(u, 1);
+        return std::min(s->cap, std::max(1, sa_width_rule(p / u, s->cap, width_r / u)));
+    };
+    int bw = batch_width(), gcap = bw;
+    GGS_HIP(launch_sa_chains_begin(s->st, g, loop, pos0, end, tries, first_it, width, width_r, bw));
+    GGS_HIP(launch_sa_chains_flags(s->st, g, pos0, tries, c.mutpb, s->N, (int*)s->flags.p));
+    GaParamsDev prm = ga_params(c, first_it, total_iters);   // sigmas replaced per neighbour from sit
+    prm.mutate_only = 1;
+    prm.o_base = 0;
+    const float bg[3] = {1.f, 1.f, 1.f};
+    SaRoundDev rd{};
+    rd.partials = (const float*)s->nb_part.p;
+    rd.wpartials = (const float*)s->wpart.p;
+    rd.nslots = 4 * s->nTiles;
+    rd.mode = c.fitness_mode;
+    rd.N = s->N;
+    rd.hw = (double)c.H * (double)c.W;
+    rd.fits_out = (float*)s->nb_fits.p;
+    rd.mutpb = c.mutpb;
+    rd.curves = (double*)s->curves.p;
+    rd.curr = (float*)s->curr.p;
+    rd.best = (float*)s->best.p;
+    rd.nb = (const float*)s->nb.p;
+    // one round: mutate + swap over the listed neighbours, one raster launch over
+    // exactly that many candidates, the chains' accept workgroups, the next list
+    auto round = [&]() -> int {
+        const int B = K * gcap;
+        {
+            ProfScope ps(s->st, 0);
+            GGS_HIP(launch_sa_chains_mutate(s->st, g, loop, sit, prm, s->N, B, (const int*)s->flags.p,
+                                            (const float*)s->curr.p, (float*)s->nb.p, (float*)s->sizes.p,
+                                            (SplatRec*)s->nb_recs.p, (int4*)s->nb_bnds.p, c.H, c.W, c.k_sigma));
+        }
+        {
+            ProfScope ps(s->st, 1);
+            if (s->multi)
+                GGS_HIP(launch_chain_strips(s->st, (const SplatRec*)s->nb_recs.p, (const int4*)s->nb_bnds.p, B, s->N,
+                                            c.H, c.W, (const float4*)s->plan.p, (float*)s->nb_part.p,
+                                            (const int*)s->order.p, g.total, g.chain, s->c->simds));
+            else
+                GGS_HIP(launch_raster(s->st, 1, (const SplatRec*)s->nb_recs.p, (const int4*)s->nb_bnds.p, B, s->N, c.H,
+                                      c.W, bg, nullptr, (const float4*)s->plan.p, (float*)s->nb_part.p,
+                                      (const int*)s->order.p, nullptr, nullptr, g.total, nullptr, s->c->simds));
+        }
+        rd.gcap = bw;
+        GGS_HIP(launch_sa_chains_accept(s->st, g, loop, sit, rd));
+        return GGS_OK;
+    };
+    // Batches of rounds with one host sync between them, as ggs_sa_run: the batch
+    // ends when every chain's pos >= end, a round consumes at most its width of a
+    // chain's tries, so ceil(longest remaining / width) rounds never overshoot.
+    int64_t remaining = end - pos0;
+    int est = gcap;
+    for (;;) {
+        int64_t R = sa_rounds_per_sync(remaining, est);
+        uint64_t ev = UINT64_MAX;
+        for (int k = 0; k < K; ++k)
+            if (unfinished(k)) ev = std::min<uint64_t>(ev, s->h_loop[k].evaluated);
+        if (ev < 64) R = std::min<int64_t>(R, 2);      // little acceptance history yet
+        for (int64_t r = 0; r < R; ++r) {
+            if ((rc = round())) return rc;
+            gcap = bw;                  // after the pending round: every round has width bw
+        }
+        GGS_HIP(hipMemcpyAsync(s->h_loop, loop, sizeof(SaLoopDev) * K, hipMemcpyDeviceToHost, s->st));
+        GGS_HIP(hipStreamSynchronize(s->st));
+        fresh = false;
+        remaining = 0;
+        int live = 1;
+        for (int k = 0; k < K; ++k) {
+            remaining = std::max<int64_t>(remaining, end - s->h_loop[k].pos);
+            live = std::max(live, (int)s->h_loop[k].live);
+        }
+        if (remaining <= 0) break;
+        bw = batch_width();
+        gcap = std::max(bw, live);      // the grids also hold the pending round
+        est = gcap;
+    }
+    std::vector<double> h(2 * tab.size());
+    GGS_HIP(hipMemcpyAsync(h.data(), s->curves.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s->st));
+    GGS_HIP(hipStreamSynchronize(s->st));
+    for (int k = 0; k < K; ++k)
+        memcpy(curves_out + 2 * (size_t)k * tstride, h.data() + 2 * (size_t)k * n, sizeof(double) * 2 * (size_t)n);
+    return GGS_OK;
+}
+
+}  // namespace
+}  // namespace ggs
+
+extern "C" {
+
+int ggs_sa_chains_create(int32_t device, const ggs_ga_config* cfg, const ggs_sa_chains* chains,
+                         const float* target_hw3, const float* mask_hw, const float* init_inds, void** handle,
+                         float* init_fits) {
+    return ggs::sc_create(device, cfg, chains, target_hw3, mask_hw, init_inds, handle, init_fits, false);
+}
+
+int ggs_sa_chains_create_targets(int32_t device, const ggs_ga_config* cfg, const ggs_sa_chains* chains,
+                                 const float* targets_khw3, const float* masks_khw, const float* init_inds,
+                                 void** handle, float* init_fits) {
+    return ggs::sc_create(device, cfg, chains, targets_khw3, masks_khw, init_inds, handle, init_fits, true);
+}
+
+int ggs_sa_chains_run(void* handle, int32_t first_it, int32_t n_its, int32_t total_iters, int32_t tries,
+                      const double* temps, int32_t width, double* curves_out) {
+    if (!handle) return fail(GGS_EINVAL, "null handle");
+    SaChains* s = (SaChains*)handle;
+    if (first_it < 0 || n_its < 0 || tries < 1) return fail(GGS_EINVAL, "need first_it >= 0, n_its >= 0, tries >= 1");
+    if (n_its > 0 && (!temps || !curves_out)) return fail(GGS_EINVAL, "null temps / curves");
+    if (width < 0 || width > s->cap) return fail(GGS_EINVAL, "width=%d outside [0, %d]", width, s->cap);
+    if ((int64_t)(first_it + (int64_t)n_its) * tries > INT32_MAX)
+        return fail(GGS_EINVAL, "iterations x tries must stay below 2^31");
+    if (n_its == 0) return GGS_OK;
+    std::lock_guard<std::mutex> lk(s->c->mu);
+    DeviceGuard dg(s->c->dev);
+    // the range in chunks that end where an exchange is due (all of it without exchange)
+    const int M = s->K >= 2 ? s->exchange_every : 0;
+    for (int done = 0; done < n_its;) {
+        const int it0 = first_it + done;
+        int n = n_its - done;
+        if (M > 0) n = std::min(n, M - it0 % M);
+        int rc = sc_run_chunk(s, it0, n, total_iters, tries, temps + done, n_its, width, curves_out + 2 * (size_t)done);
+        if (rc) return rc;
+        const int it = it0 + n - 1;
+        if (M > 0 && (it + 1) % M == 0) {
+            const SaChainsDev g = sc_dev(s, n, n * tries);
+            GGS_HIP(launch_sa_chains_exchange(s->st, g, (SaLoopDev*)s->loop.p, (const SaItDev*)s->sit.p, n - 1, it,
+                                              s->exchange_seed, (it + 1) / M - 1, s->N, (float*)s->curr.p,
+                                              (float*)s->best.p, (unsigned long long*)s->swaps.p));
+            GGS_HIP(hipMemcpyAsync(s->h_loop, s->loop.p, sizeof(SaLoopDev) * s->K, hipMemcpyDeviceToHost, s->st));
+            GGS_HIP(hipMemcpyAsync(s->h_swaps, s->swaps.p, sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost,
+                                   s->st));
+            GGS_HIP(hipStreamSynchronize(s->st));
+        }
+        done += n;
+    }
+    return GGS_OK;
+}
+
+int ggs_sa_chains_state(void* handle, double* best_fit, double* curr_fit, uint64_t* rounds, uint64_t* evaluated,
+                        uint64_t* accepted, uint64_t* swaps_tried, uint64_t* swaps_accepted) {
+    if (!handle) return fail(GGS_EINVAL, "null handle");
+    SaChains* s = (SaChains*)handle;
+    std::lock_guard<std::mutex> lk(s->c->mu);
+    for (int k = 0; k < s->K; ++k) {    // as of the end of the last ggs_sa_chains_run (or creation)
+        const SaLoopDev& l = s->h_loop[k];
+        if (best_fit) best_fit[k] = l.best_fit;
+        if (curr_fit) curr_fit[k] = l.curr_fit;
+        if (rounds) rounds[k] = l.rounds;
+        if (evaluated) evaluated[k] = l.evaluated;
+        if (accepted) accepted[k] = l.accepted;
+    }
+    if (swaps_tried) *swaps_tried = s->h_swaps[0];
+    if (swaps_accepted) *swaps_accepted = s->h_swaps[1];
+    return GGS_OK;
+}
+
+int ggs_sa_chains_read(void* handle, float* current, float* best) {
+    if (!handle) return fail(GGS_EINVAL, "null handle");
+    SaChains* s = (SaChains*)handle;
+    std::lock_guard<std::mutex> lk(s->c->mu);
+    DeviceGuard dg(s->c->dev);
+    const size_t n9 = 9 * (size_t)s->N;
+    GGS_HIP(hipStreamSynchronize(s->st));
+    for (int k = 0; k < s->K && n9; ++k) {
+        if (current)
+            GGS_HIP(hipMemcpy(current + n9 * k, (const float*)s->curr.p + k * s->gstride, sizeof(float) * n9,
+                              hipMemcpyDeviceToHost));
+        if (best)
+            GGS_HIP(hipMemcpy(best + n9 * k, (const float*)s->best.p + k * s->gstride, sizeof(float) * n9,
+                              hipMemcpyDeviceToHost));
+    }
+    return GGS_OK;
+}
+
+void ggs_sa_chains_destroy(void* handle) {
+    if (!handle) return;
+    SaChains* s = (SaChains*)handle;
+    {
+        std::lock_guard<std::mutex> lk(s->c->mu);
+        DeviceGuard dg(s->c->dev);
+        if (s->st) (void)hipStreamSynchronize(s->st);
+        sc_free(s);
+    }
+    delete s;
+}
+
+int ggs_sa_exchange_uniform(uint64_t exchange_seed, int32_t it, int32_t k, double* u) {
+    if (!u || it < 0 || k < 0) return fail(GGS_EINVAL, "bad arguments");
+    *u = sa_exchange_uniform(exchange_seed, (uint32_t)it, (uint32_t)k);
+    return GGS_OK;
+}
+
+}  // extern "C"

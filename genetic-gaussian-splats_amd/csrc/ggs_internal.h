@@ -239,6 +239,54 @@ hipError_t launch_sa_mutate(hipStream_t st, const SaLoopDev* sl, const SaItDev* 
 // in [0, 1).  Host and device compute the same bits.
 double sa_accept_uniform(uint64_t seed, uint32_t it, uint32_t k);
 
+// ---- SA chain groups (ggs_sa_chains_*) -----------------------------------------
+// K chains, each the device SA loop above with its own SaLoopDev, Philox seed,
+// temperatures and (optionally) target plan.  Every array gains a leading chain
+// dimension: loop state [K], iteration table [K][n_its], flags [K][n_tries],
+// curves [K][n_its][2], current / best genomes [K] rows of gstride floats.  The
+// round's neighbours of all chains are one raster batch, named by the compact
+// candidate list: a chain at high acceptance has one live neighbour while a cold
+// one has the batch width, and a chain that finished the chunk has none.
+constexpr int kSaMaxChains = GGS_SA_MAX_CHAINS;
+struct SaChainsDev {
+    int K, n_its, n_tries, cap; // chains; iterations and tries of the chunk; neighbour capacity per chain
+    int64_t gstride;            // floats between the chains' genomes (N * 9 rounded up to 4: 16-B rows)
+    int64_t wstride;            // floats between the chains' plan weight blocks (0: one shared plan)
+    const uint64_t* seeds;      // [K]
+    int* total;                 // candidates of the round (the raster's `live`)
+    int* base;                  // [K] chain k's first candidate
+    int* chain;                 // [K * cap] candidate b's chain (per-target: its plan)
+    int* slot;                  // [K * cap] candidate b's slot in its chain's round
+};
+// Start a chunk for every chain and write the first round's list.
+hipError_t launch_sa_chains_begin(hipStream_t st, const SaChainsDev& g, SaLoopDev* sl, int64_t pos, int64_t end,
+                                  int tries, int first_it, int width, double width_r, int gcap);
+hipError_t launch_sa_chains_flags(hipStream_t st, const SaChainsDev& g, int64_t pos0, int tries, float mutpb, int N,
+                                  int* tflags);
+// The listed neighbours (launch_sa_mutate per candidate): off [B][N][9], sizes [B][N],
+// recs / bnds [B][N], B = the launch's candidate capacity (grid size).
+hipError_t launch_sa_chains_mutate(hipStream_t st, const SaChainsDev& g, const SaLoopDev* sl, const SaItDev* sit,
+                                   const GaParamsDev& prm, int N, int B, const int* tflags, const float* curr,
+                                   float* off, float* sizes, SplatRec* recs, int4* bnds, int H, int W,
+                                   float k_sigma);
+// launch_sa_accept for every chain (r: the group's base pointers; r.seed is
+// replaced by the chain's), then the next round's list.
+hipError_t launch_sa_chains_accept(hipStream_t st, const SaChainsDev& g, SaLoopDev* sl, const SaItDev* sit,
+                                   const SaRoundDev& r);
+// Replica exchange e after iteration `it` (row ii of the iteration table), in
+// place; swaps [2] accumulates pairs tried / swapped.
+hipError_t launch_sa_chains_exchange(hipStream_t st, const SaChainsDev& g, SaLoopDev* sl, const SaItDev* sit, int ii,
+                                     int it, uint64_t xseed, int e, int N, float* curr, float* best,
+                                     unsigned long long* swaps);
+// The exchange uniform of pair (k, k + 1) after iteration it: accept_u's Philox
+// block with what = 1.  Host and device compute the same bits.
+double sa_exchange_uniform(uint64_t seed, uint32_t it, uint32_t k);
+// The fitness raster of a chain group with a target per chain: candidate b < *live
+// is scored against plan plan_of[b] of a plan set (unfused: partials only).
+hipError_t launch_chain_strips(hipStream_t st, const SplatRec* recs, const int4* bnds, int B, int N, int H, int W,
+                               const float4* plans, float* partials, const int* tile_order, const int* live,
+                               const int* plan_of, int simds);
+
 struct BreedDev {               // the fused breed (launch_ga_variation with br != null)
     const float* pop_prev;      // [P][N][9] population P_{g-1} (materialised)
     const float* fits_prev;     // [P] its fitness

@@ -350,7 +350,7 @@ __device__ __forceinline__ f2_t fma2(f2_t a, f2_t b, f2_t c) { return __builtin_
 // raster_body is the one kernel body; its entry points are raster_kernel (one
 // target plan per launch) and raster_multi_kernel (a plan set: candidate b is
 // scored against plan b / group, MULTI).
-template <int MODE, bool SAT, bool FUSED, bool MULTI>
+template <int MODE, bool SAT, bool FUSED, bool MULTI, bool LIST = false>
 __device__ __forceinline__ void
 raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, int B, int N, int H, int W, int nTX,
             int nTiles,
@@ -358,8 +358,9 @@ raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, in
             const float4* __restrict__ plan, float* __restrict__ partials,
             const int* __restrict__ tile_order, const unsigned char* __restrict__ dirty,
             const float* __restrict__ clean, const int* __restrict__ live, int CH, FinFused fin, int simds,
-            int group) {
+            int group, const int* __restrict__ plan_of = nullptr) {
     static_assert(!MULTI || MODE == 1, "plan sets are for the fitness epilogue");
+    static_assert(!LIST || MULTI, "a plan list names plans of a plan set");
     constexpr bool DS = GGS_DEPTH_SPLIT && MODE == 1 && !SAT;
     // cull-list words carry the visit's scalar control (visit_word): the instances
     // without the saturation check and the folded finalize (in the GA's folded
@@ -422,7 +423,8 @@ raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, in
     const int b = b0 + (int)((idx + (gi >> (SAT ? XCD_SHIFT : 0))) % Bc);
     // a plan set: the candidate's plan, divided here (the division's VALU temporaries
     // would spill at the epilogue's register peak) and kept in one SGPR
-    const int pk = MULTI ? ufirst(b / group) : 0;
+    // (LIST, the SA chain groups: the plan is named by a list, one scalar load)
+    const int pk = LIST ? ufirst(plan_of[b]) : MULTI ? ufirst(b / group) : 0;
     const int t = grp / SPB;
     const int wv = (grp % SPB) * WPB + wib;           // strip 0..3 of the tile
     const int tx0 = (t % nTX) * TILE;
@@ -1008,6 +1010,24 @@ raster_multi_kernel(const SplatRec* __restrict__ recs, const int4* __restrict__ 
                                      tile_order, nullptr, nullptr, nullptr, CH, fin, simds, group);
 }
 
+// The fitness raster of an SA chain group with a target per chain: the first
+// *live candidates of the launch are the round's compact candidate list, and
+// candidate b reads plan plan_of[b] of the plan set (its chain).  Unfused: the
+// chains' accept kernel reduces the partials.  The name says "strips", not
+// what the body is called: tests/test_kernel_resources*.py count the code
+// object's kernels by that word (10 entry points, 6 of them the single-plan
+// kernel), and these two are counted by tests/test_kernel_resources_chains.py.
+template <bool SAT>
+__global__ void __launch_bounds__(GGS_DEPTH_SPLIT ? 2 * NT : NT, OCC)
+chain_strips_kernel(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, int B, int N, int H, int W,
+                    int nTX, int nTiles, float bg_r, float bg_g, float bg_b, const float4* __restrict__ plan,
+                    float* __restrict__ partials, const int* __restrict__ tile_order,
+                    const int* __restrict__ live, int CH, int simds, const int* __restrict__ plan_of) {
+    raster_body<1, SAT, false, true, true>(recs, bnds, B, N, H, W, nTX, nTiles, bg_r, bg_g, bg_b, nullptr, plan,
+                                           partials, tile_order, nullptr, nullptr, live, CH, FinFused{}, simds, 1,
+                                           plan_of);
+}
+
 // ---------------------------------------------------------------------------
 // target plan: the fitness epilogue's inputs re-laid out in raster lane order
 // ---------------------------------------------------------------------------
@@ -1301,6 +1321,25 @@ hipError_t launch_raster(hipStream_t st, int mode, const SplatRec* recs, const i
     else { if (!sat) GGS_RASTER(1, false, true); else GGS_RASTER(1, true, true); }  // + folded finalize
 #undef GGS_RASTER_MULTI
 #undef GGS_RASTER
+    return hipGetLastError();
+}
+
+hipError_t launch_chain_strips(hipStream_t st, const SplatRec* recs, const int4* bnds, int B, int N, int H, int W,
+                               const float4* plans, float* partials, const int* tile_order, const int* live,
+                               const int* plan_of, int simds) {
+    int nTX;
+    const int nTiles = raster_tiles(H, W, &nTX);
+    if (!live || !plan_of) return hipErrorInvalidValue;
+    const bool sat = N > SAT_MIN_SPLATS;
+    const dim3 grid((unsigned)((int64_t)B * nTiles * SPB)), block(GGS_DEPTH_SPLIT && !sat ? 2 * NT : NT);
+    const int CH = raster_chunk(N);
+    if (GGS_DEPTH_SPLIT) simds = 0;
+    if (!sat)
+        hipLaunchKernelGGL(chain_strips_kernel<false>, grid, block, 0, st, recs, bnds, B, N, H, W, nTX, nTiles, 1.f,
+                           1.f, 1.f, plans, partials, tile_order, live, CH, simds, plan_of);
+    else
+        hipLaunchKernelGGL(chain_strips_kernel<true>, grid, block, 0, st, recs, bnds, B, N, H, W, nTX, nTiles, 1.f,
+                           1.f, 1.f, plans, partials, tile_order, live, CH, simds, plan_of);
     return hipGetLastError();
 }
 

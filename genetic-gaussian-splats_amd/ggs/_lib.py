@@ -40,6 +40,12 @@ class GaDraws(C.Structure):
                 ("n_rgba", _f32p), ("swap_i", _i32p), ("swap_pick", _i32p), ("swap_u", _f64p)]
 
 
+class SaChains(C.Structure):
+    """ggs_sa_chains (include/ggs.h)."""
+    _fields_ = [("n_chains", C.c_int32), ("exchange_every", C.c_int32), ("seeds", C.POINTER(C.c_uint64)),
+                ("exchange_seed", C.c_uint64)]
+
+
 class GaIslands(C.Structure):
     """ggs_ga_islands (include/ggs.h)."""
     _fields_ = [("n_islands", C.c_int32), ("migrate_every", C.c_int32), ("n_migrants", C.c_int32),
@@ -122,6 +128,18 @@ SIGNATURES = {
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint64)]),
     "ggs_sa_accept_uniform": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
+    "ggs_sa_chains_create": (C.c_int, [C.c_int32, C.POINTER(GaConfig), C.POINTER(SaChains), _f32p, _f32p, _f32p,
+                                       C.POINTER(C.c_void_p), _f32p]),
+    "ggs_sa_chains_create_targets": (C.c_int, [C.c_int32, C.POINTER(GaConfig), C.POINTER(SaChains), _f32p,
+                                               _f32p, _f32p, C.POINTER(C.c_void_p), _f32p]),
+    "ggs_sa_chains_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double)]),
+    "ggs_sa_chains_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ggs_sa_chains_read": (C.c_int, [C.c_void_p, _f32p, _f32p]),
+    "ggs_sa_chains_destroy": (None, [C.c_void_p]),
+    "ggs_sa_exchange_uniform": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     # ggs_ga_draws_out is ggs_ga_draws with writable arrays: one ctypes structure serves both
     "ggs_ga_philox_draws": (C.c_int, [C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_float, C.POINTER(GaDraws)]),

@@ -72,7 +72,7 @@ def simulated_annealing(target_img_uint8, H: int, W: int, device, n_splats: int,
                         init_individual: Optional[np.ndarray] = None, progress: bool = True,
                         return_state: bool = False, speculate: Optional[int] = None,
                         backend: str = "auto", incremental: bool = False, loop: str = "auto",
-                        chunk: int = 256):
+                        chunk: int = 256, chains: int = 1, temp_ladder=None, exchange_every: int = 0):
     """annealing.py:47-190 → (best individual [N, 9] float32, best energy).
 
     Keyword-only hooks as ggs.ga.genetic_approx (``seed``, ``draws`` — a source
@@ -90,7 +90,35 @@ def simulated_annealing(target_img_uint8, H: int, W: int, device, n_splats: int,
     module doc; device backend, Philox draws), "host" (acceptance test in Python)
     or "auto" (device when possible).  ``chunk``: iterations per ``ggs_sa_run``
     call in the device loop (progress bar / interrupt granularity; video frames
-    fall on chunk ends)."""
+    fall on chunk ends).
+
+    ``chains`` = K > 1 anneals K chains on the image in one device session
+    (``ga_device.DeviceSAChains``; device backend and loop, Philox draws, no
+    frames).  Chain k is seeded ``(seed + k) mod 2^64`` and starts from
+    ``new_population(..., default_rng(seed_k))`` (``init_individual``, when given,
+    is [K, N, 9], or [N, 9] for all chains); its temperatures are
+    ``temp_schedule(kind, temp0 * temp_ladder[k], it, total)``, ``temp_ladder``
+    defaulting to all ones.  Chain 0 without exchange is the ``chains=1`` run.
+    ``exchange_every`` = M > 0 adds replica exchange between neighbouring chains
+    after every M-th iteration (``replica_exchange``, keyed by ``seed``).  Returns
+    the best chain's (individual, energy); with ``return_state`` the state holds
+    ``"best_chain"`` and ``"chains"``, a list of per-chain ``{"best", "best_fit",
+    "current", "current_fit", "curves", "accepted", "rounds", "evaluated"}``, and
+    the exchange counts.  ``chains=1`` is the code path above, untouched."""
+    chains = int(chains)
+    if chains < 1:
+        raise ValueError(f"chains must be >= 1, got {chains}")
+    if chains > 1:
+        if draws is not None or evaluate is not None or backend not in ("auto", "device") \
+                or loop not in ("auto", "device") or incremental:
+            raise ValueError("chains > 1 needs the device backend and loop with the in-kernel (Philox) "
+                             "draws, without incremental evaluation")
+        return _simulated_annealing_chains(
+            target_img_uint8, H, W, device, n_splats, mutpb, mut_sigma_max, mut_sigma_min,
+            sigma_schedule, min_scale_splats, max_scale_splats, k_sigma, mask_strength, boost_only,
+            iterations, temp0, temp_schedule, tries_per_iter, prefix, loss_png_path, loss_csv_path,
+            loss_log_y, seed, init_individual, progress, return_state, speculate, chunk, chains,
+            temp_ladder, int(exchange_every))
     from .mask import compute_importance_mask, prepare_target
     from .ga import resolve_seed
     seed = resolve_seed(seed)                                # run_sags.py:26-27 seeds `random`
@@ -225,6 +253,243 @@ def simulated_annealing(target_img_uint8, H: int, W: int, device, n_splats: int,
         prop.close()
     return _finish(best, best_fit, curr, curr_fit, curves, stats, prefix, loss_png_path,
                    loss_csv_path, loss_log_y, return_state)
+
+
+def replica_exchange(curr, curr_fit, best, best_fit, temps_at_it, it: int, M: int, exchange_seed: int):
+    """Replica exchange after iteration ``it`` of K chains on one image, the numpy
+    statement the device kernel is held to (ggs_sa_chains_run, include/ggs.h).
+
+    ``curr`` / ``best`` [K, N, 9], ``curr_fit`` / ``best_fit`` [K] (float64, the
+    widened float32 energies), ``temps_at_it`` [K] the chains' temperatures of
+    iteration ``it``; (it + 1) % M must be 0.  Exchange e = (it + 1) / M - 1
+    considers the pairs (k, k + 1) with k % 2 == e % 2, all from the pre-exchange
+    state: d = (E_k - E_{k+1}) (1 / T_k - 1 / T_{k+1}), swap iff u < exp(d) with
+    u = ggs_sa_exchange_uniform(exchange_seed, it, k); a pair with a temperature
+    <= 0 is skipped and not counted.  A swap trades current genome and energy;
+    each chain of the pair then applies annealing.py:148-150.  Returns new
+    (curr, curr_fit, best, best_fit, tried, accepted); the inputs are not modified."""
+    import ctypes as C
+    from ._lib import check, lib
+    if M < 1 or (it + 1) % M != 0:
+        raise ValueError(f"no exchange is due after iteration {it} with exchange_every={M}")
+    c0, b0 = np.asarray(curr, np.float32), np.asarray(best, np.float32)
+    f0 = np.asarray(curr_fit, np.float64)
+    c, b = c0.copy(), b0.copy()
+    cf, bf = f0.copy(), np.array(best_fit, np.float64, copy=True)
+    T = np.asarray(temps_at_it, np.float64)
+    K = len(f0)
+    e = (it + 1) // M - 1
+    tried = accepted = 0
+    for k in range(e % 2, K - 1, 2):
+        if not (T[k] > 0.0 and T[k + 1] > 0.0):
+            continue
+        d = float((f0[k] - f0[k + 1]) * (1.0 / T[k] - 1.0 / T[k + 1]))
+        u = C.c_double()
+        check(lib.ggs_sa_exchange_uniform(int(exchange_seed) & (2**64 - 1), int(it), int(k), C.byref(u)),
+              "ggs_sa_exchange_uniform")
+        tried += 1
+        if d >= 0.0 or u.value < math.exp(d):          # (d >= 0: exp(d) >= 1 > u, and no overflow)
+            accepted += 1
+            c[k], c[k + 1] = c0[k + 1], c0[k]
+            cf[k], cf[k + 1] = f0[k + 1], f0[k]
+            for q in (k, k + 1):
+                if cf[q] + 1e-12 < bf[q]:               # annealing.py:148-150
+                    bf[q] = cf[q]
+                    b[q] = c[q]
+    return c, cf, b, bf, tried, accepted
+
+
+def chain_seeds(seed: int, K: int):
+    """Philox seeds of the K chains (images) of a group: (seed + k) mod 2^64, so
+    chain 0 keeps the run's seed."""
+    return [(int(seed) + k) % 2**64 for k in range(K)]
+
+
+def _chains_loop(sa, K, iterations, tries, temps_of, width, chunk, progress, desc):
+    """``_device_loop`` for a chain group: ``chunk`` iterations of all chains per
+    ggs_sa_chains_run call.  temps_of(k, i): chain k's temperature of iteration i.
+    Returns per-chain curves (lists of (best, current) columns) and the state."""
+    bar = None
+    if progress:
+        try:
+            from tqdm.auto import tqdm
+            bar = tqdm(total=iterations, desc=desc, leave=True)
+        except ImportError:
+            pass
+    st = sa.loop_state()
+    curves = [{"best": [float(st["best_fit"][k])], "current": [float(st["current_fit"][k])]}
+              for k in range(K)]
+    it = 0
+    t0 = time.perf_counter()
+    try:
+        while it < iterations:
+            n = min(max(1, int(chunk)), iterations - it)
+            if tries:
+                temps = [[temps_of(k, i) for i in range(it, it + n)] for k in range(K)]
+                cv = sa.run(it, temps, iterations, tries, width)
+                st = sa.loop_state()
+            for k in range(K):
+                if tries:
+                    curves[k]["best"].extend(cv[k, :, 0].tolist())
+                    curves[k]["current"].extend(cv[k, :, 1].tolist())
+                else:                    # no tries: the state never moves
+                    curves[k]["best"].extend([float(st["best_fit"][k])] * n)
+                    curves[k]["current"].extend([float(st["current_fit"][k])] * n)
+            it += n
+            if bar is not None:
+                bar.update(n)
+                bar.set_postfix(best_mse=f"{float(np.min(st['best_fit'])):.6f}")
+    except KeyboardInterrupt:
+        print("\n[Interrupted] Returning current best…", flush=True)
+    finally:
+        if bar is not None:
+            bar.close()
+    st["loop_s"] = time.perf_counter() - t0
+    st["tries"] = it * tries
+    return curves, st
+
+
+def _chain_states(sa, curves, st, K):
+    cur, best = sa.read()
+    return [{"best": best[k], "best_fit": float(st["best_fit"][k]), "current": cur[k],
+             "current_fit": float(st["current_fit"][k]), "curves": curves[k],
+             "accepted": int(st["accepted"][k]), "rounds": int(st["rounds"][k]),
+             "evaluated": int(st["evaluated"][k])} for k in range(K)]
+
+
+def _group_stats(st):
+    return {"evaluated": int(np.sum(st["evaluated"])), "tries": st["tries"],
+            "launches": int(np.max(st["rounds"])), "accepted": int(np.sum(st["accepted"])),
+            "loop_s": st["loop_s"], "swaps_tried": st["swaps_tried"],
+            "swaps_accepted": st["swaps_accepted"]}
+
+
+def _simulated_annealing_chains(img, H, W, device, n_splats, mutpb, mut_sigma_max, mut_sigma_min,
+                                sigma_schedule, min_scale_splats, max_scale_splats, k_sigma,
+                                mask_strength, boost_only, iterations, temp0, sched, tries_per_iter,
+                                prefix, loss_png_path, loss_csv_path, loss_log_y, seed, init_individual,
+                                progress, return_state, speculate, chunk, K, temp_ladder, exchange_every):
+    from . import api
+    from .ga import resolve_seed
+    from .ga_device import DeviceSAChains
+    from .mask import compute_importance_mask, prepare_target
+    seed = resolve_seed(seed)
+    ladder = [1.0] * K if temp_ladder is None else [float(x) for x in temp_ladder]
+    if len(ladder) != K:
+        raise ValueError(f"temp_ladder must have one factor per chain ({K}), got {len(ladder)}")
+    t = prepare_target(img, H, W)
+    imp_mask = compute_importance_mask(t, H, W, edge_scales=(1, 2, 4), w_edge=0.7, w_var=0.3,
+                                       gamma=0.7, floor=0.15, smooth=3, strength=mask_strength)
+    seeds = chain_seeds(seed, K)
+    if init_individual is not None:
+        inds = np.array(init_individual, np.float32, copy=True)
+        if inds.ndim == 2:
+            inds = np.repeat(inds[None], K, axis=0)
+        if inds.ndim != 3 or inds.shape[0] != K:
+            raise ValueError(f"init_individual must be [N, 9] or [K={K}, N, 9], got {inds.shape}")
+    else:
+        inds = np.stack([new_population(1, n_splats, H, W, min_scale_splats, max_scale_splats,
+                                        np.random.default_rng(sk))[0] for sk in seeds])
+    tries = max(0, int(tries_per_iter))
+    cap = max(1, int(speculate)) if speculate is not None else device_loop_width(H, W, tries)
+    sa = DeviceSAChains(t, imp_mask, inds, seeds, exchange_every=exchange_every, exchange_seed=seed,
+                        max_tries=cap, mutpb=mutpb, mut_sigma_max=mut_sigma_max,
+                        mut_sigma_min=mut_sigma_min, schedule=sigma_schedule,
+                        min_scale_splats=min_scale_splats, max_scale_splats=max_scale_splats,
+                        k_sigma=k_sigma, boost_only=boost_only, device=api.device_index(device))
+    try:
+        curves, st = _chains_loop(sa, K, iterations, tries,
+                                  lambda k, i: _T(sched, temp0 * ladder[k], i, iterations),
+                                  0 if speculate is None else max(1, int(speculate)), chunk, progress,
+                                  f"SA iterations ({K} chains)")
+        states = _chain_states(sa, curves, st, K)
+    finally:
+        sa.close()
+    kb = int(np.argmin([c["best_fit"] for c in states]))      # the first one on ties
+    w = states[kb]
+    out = _finish(w["best"], w["best_fit"], w["current"], w["current_fit"], w["curves"],
+                  _group_stats(st), prefix, loss_png_path, loss_csv_path, loss_log_y, return_state)
+    if return_state:
+        out[2]["best_chain"] = kb
+        out[2]["chains"] = states
+    return out
+
+
+def simulated_annealing_many(images, H: int, W: int, device, n_splats: int, mutpb: float,
+                             mut_sigma_max: dict, mut_sigma_min: dict, sigma_schedule: str,
+                             min_scale_splats: float, max_scale_splats: float, k_sigma: float,
+                             mask_strength: float, boost_only: bool, iterations: int, temp0: float,
+                             temp_schedule: str, tries_per_iter: int = 1, *,
+                             seed: Optional[int] = None, init_individual: Optional[np.ndarray] = None,
+                             progress: bool = True, return_state: bool = False,
+                             speculate: Optional[int] = None, chunk: int = 256, prep: str = "host"):
+    """``simulated_annealing`` (device backend and loop) for K images in one session:
+    a chain group with a target per chain (``ga_device.DeviceSAChains`` with a 4-D
+    target), the SA counterpart of ``ga.genetic_approx_many``.
+
+    Each image goes through ``prepare_target`` and ``compute_importance_mask`` as in
+    ``simulated_annealing``; image k is seeded ``(seed + k) mod 2^64`` and starts
+    from ``new_population(..., default_rng(seed_k))[0]`` (``init_individual``, when
+    given, is [K, N, 9]).  Image k's result is that of ``simulated_annealing(
+    images[k], ..., seed=seed + k)``, bit for bit.  ``prep="device"`` prepares the K
+    targets and masks on the device (``mask.prepare_targets``, within 2e-5 of the
+    host's).
+
+    Returns a list of K ``(best individual [N, 9], best energy)``; with
+    ``return_state`` each entry is ``(best, energy, {"current", "current_fit",
+    "curves", "accepted", "rounds", "evaluated"})``.  No frames, CSV or PNG outputs."""
+    from . import api
+    from .ga import resolve_seed
+    from .ga_device import DeviceSAChains
+    from .mask import compute_importance_mask, prepare_target, prepare_targets
+    images = list(images)
+    K = len(images)
+    if K < 1:
+        raise ValueError("simulated_annealing_many needs at least one image")
+    if prep not in ("host", "device"):
+        raise ValueError(f"prep must be 'host' or 'device', got {prep!r}")
+    seed = resolve_seed(seed)
+    seeds = chain_seeds(seed, K)
+    sched = temp_schedule
+    if prep == "device":
+        targets, masks = prepare_targets(images, H, W, edge_scales=(1, 2, 4), w_edge=0.7, w_var=0.3,
+                                         gamma=0.7, floor=0.15, smooth=3, strength=mask_strength,
+                                         backend="device", device=device)
+    else:
+        targets = np.stack([prepare_target(im, H, W) for im in images])
+        masks = np.stack([compute_importance_mask(t, H, W, edge_scales=(1, 2, 4), w_edge=0.7, w_var=0.3,
+                                                  gamma=0.7, floor=0.15, smooth=3, strength=mask_strength)
+                          for t in targets])
+    if init_individual is not None:
+        inds = np.array(init_individual, np.float32, copy=True)
+        if inds.ndim != 3 or inds.shape[0] != K:
+            raise ValueError(f"init_individual must be [K={K}, N, 9], got {inds.shape}")
+    else:
+        inds = np.stack([new_population(1, n_splats, H, W, min_scale_splats, max_scale_splats,
+                                        np.random.default_rng(sk))[0] for sk in seeds])
+    tries = max(0, int(tries_per_iter))
+    cap = max(1, int(speculate)) if speculate is not None else device_loop_width(H, W, tries)
+    sa = DeviceSAChains(targets, masks, inds, seeds, max_tries=cap, mutpb=mutpb,
+                        mut_sigma_max=mut_sigma_max, mut_sigma_min=mut_sigma_min,
+                        schedule=sigma_schedule, min_scale_splats=min_scale_splats,
+                        max_scale_splats=max_scale_splats, k_sigma=k_sigma, boost_only=boost_only,
+                        device=api.device_index(device))
+    try:
+        curves, st = _chains_loop(sa, K, iterations, tries,
+                                  lambda k, i: _T(sched, temp0, i, iterations),
+                                  0 if speculate is None else max(1, int(speculate)), chunk, progress,
+                                  f"SA iterations (device, {K} images)")
+        states = _chain_states(sa, curves, st, K)
+    finally:
+        sa.close()
+    out = []
+    for c in states:
+        if return_state:
+            out.append((c["best"], c["best_fit"], {q: c[q] for q in ("current", "current_fit", "curves",
+                                                                      "accepted", "rounds", "evaluated")}))
+        else:
+            out.append((c["best"], c["best_fit"]))
+    return out
 
 
 def device_loop_width(H: int, W: int, tries: int) -> int:

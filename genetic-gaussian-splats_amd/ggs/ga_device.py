@@ -159,6 +159,109 @@ class DeviceSA:
             pass
 
 
+class DeviceSAChains:
+    """K device-resident SA chains in one session (ggs_sa_chains_* in include/ggs.h):
+    one set of launches per round for all chains, one raster launch over exactly
+    the neighbours they have live.  ``init_inds`` is [K, N, 9], ``seeds`` [K];
+    chain k without exchange follows ``DeviceSA(seed=seeds[k], init_ind=
+    init_inds[k])`` run with ``temps[k]`` bit for bit.  ``max_tries`` is the
+    neighbour capacity per chain.
+
+    A 4-D ``target`` [K, H, W, 3] (with ``mask`` [K, H, W] or None) gives every
+    chain its own image (ggs_sa_chains_create_targets); a 3-D target is shared by
+    all chains, and only then may ``exchange_every`` = M > 0 ask for replica
+    exchange after every iteration ``it`` with (it + 1) % M == 0
+    (``ggs.annealing.replica_exchange`` states the rule)."""
+
+    def __init__(self, target, mask, init_inds, seeds, *, exchange_every: int = 0,
+                 exchange_seed: int = 0, max_tries: int, mutpb: float,
+                 mut_sigma_max: Dict[str, float], mut_sigma_min: Dict[str, float],
+                 schedule: str, min_scale_splats: float, max_scale_splats: float,
+                 k_sigma: float = 3.0, boost_only: bool = False, boost_beta: float = 1.0,
+                 device: int = 0):
+        inds = _arr(init_inds, np.float32)
+        if inds.ndim != 3 or inds.shape[2] != 9:
+            raise _lib.GGSInputError("the chain group keeps [K, N, 9] genomes")
+        K, N, _ = inds.shape
+        sd = np.asarray([int(s) & (2**64 - 1) for s in seeds], np.uint64)
+        if sd.shape != (K,):
+            raise _lib.GGSInputError(f"seeds must have one entry per chain ({K}), got {sd.shape}")
+        self.target = _arr(target, np.float32)
+        self.mask = None if mask is None else _arr(mask, np.float32)
+        self.per_chain = self.target.ndim == 4
+        if self.per_chain:
+            if self.target.shape[0] != K or self.target.shape[3] != 3:
+                raise _lib.GGSInputError(
+                    f"per-chain targets must be [K={K}, H, W, 3], got {self.target.shape}")
+            if self.mask is not None and self.mask.shape != self.target.shape[:3]:
+                raise _lib.GGSInputError(
+                    f"per-chain masks must be {self.target.shape[:3]}, got {self.mask.shape}")
+        elif self.target.ndim != 3:
+            raise _lib.GGSInputError(f"target must be [H, W, 3] or [K, H, W, 3], got {self.target.shape}")
+        H, W = self.target.shape[-3:-1]
+        self.K, self.N, self.H, self.W, self.cap = K, N, H, W, max(1, int(max_tries))
+        cfg = _config(self.cap, N, H, W, 1, 0, 0.0, mutpb, k_sigma, min_scale_splats,
+                      max_scale_splats, self.mask, boost_only, boost_beta, schedule,
+                      mut_sigma_max, mut_sigma_min, 0)
+        ch = _lib.SaChains(K, int(exchange_every), sd.ctypes.data_as(C.POINTER(C.c_uint64)),
+                           int(exchange_seed) & (2**64 - 1))
+        h = C.c_void_p()
+        fits = np.empty(K, np.float32)
+        # arguments are validated before the library looks for a device
+        create, name = ((lib.ggs_sa_chains_create_targets, "ggs_sa_chains_create_targets")
+                        if self.per_chain else (lib.ggs_sa_chains_create, "ggs_sa_chains_create"))
+        check(create(device, C.byref(cfg), C.byref(ch), self.target.ctypes.data_as(_f32p),
+                     None if self.mask is None else self.mask.ctypes.data_as(_f32p),
+                     inds.ctypes.data_as(_f32p), C.byref(h), fits.ctypes.data_as(_f32p)), name)
+        self.h, self.init_fits = h, fits
+
+    def run(self, first_it: int, temps, total: int, tries: int, width: int = 0) -> np.ndarray:
+        """Iterations first_it .. first_it+n-1 of every chain (ggs_sa_chains_run),
+        ``temps`` [K, n].  Returns the [K, n, 2] (best, current) energy curves."""
+        t = _arr(temps, np.float64)
+        if t.ndim != 2 or t.shape[0] != self.K:
+            raise _lib.GGSInputError(f"temps must be [K={self.K}, n], got {t.shape}")
+        out = np.empty((self.K, t.shape[1], 2), np.float64)
+        check(lib.ggs_sa_chains_run(self.h, int(first_it), t.shape[1], int(total), int(tries),
+                                    t.ctypes.data_as(_f64p), int(width), out.ctypes.data_as(_f64p)),
+              "ggs_sa_chains_run")
+        return out
+
+    def loop_state(self) -> Dict[str, object]:
+        """Per-chain energies and counters ([K] arrays) after the last ``run``, and
+        the session's exchange counts."""
+        K = self.K
+        b, c = np.empty(K, np.float64), np.empty(K, np.float64)
+        r, e, a = np.empty(K, np.uint64), np.empty(K, np.uint64), np.empty(K, np.uint64)
+        st, sa = C.c_uint64(), C.c_uint64()
+        u64p = C.POINTER(C.c_uint64)
+        check(lib.ggs_sa_chains_state(self.h, b.ctypes.data_as(_f64p), c.ctypes.data_as(_f64p),
+                                      r.ctypes.data_as(u64p), e.ctypes.data_as(u64p),
+                                      a.ctypes.data_as(u64p), C.byref(st), C.byref(sa)),
+              "ggs_sa_chains_state")
+        return {"best_fit": b, "current_fit": c, "rounds": r, "evaluated": e, "accepted": a,
+                "swaps_tried": st.value, "swaps_accepted": sa.value}
+
+    def read(self):
+        """(current [K, N, 9], best [K, N, 9])."""
+        cur = np.empty((self.K, self.N, 9), np.float32)
+        best = np.empty((self.K, self.N, 9), np.float32)
+        check(lib.ggs_sa_chains_read(self.h, cur.ctypes.data_as(_f32p), best.ctypes.data_as(_f32p)),
+              "ggs_sa_chains_read")
+        return cur, best
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            lib.ggs_sa_chains_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 — interpreter shutdown
+            pass
+
+
 class DeviceGA:
     """One device-resident GA population (see module docstring)."""
 

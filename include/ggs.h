@@ -383,6 +383,64 @@ int ggs_sa_set_incremental(void* handle, int32_t on);
 int ggs_sa_stats(void* handle, uint64_t* proposed, uint64_t* changed_splats);
 void ggs_sa_destroy(void* handle);
 
+/* ---- SA chain groups: K annealing chains in one session ---------------------
+ * K chains of the device loop above (ggs_sa_run) in one session: one set of
+ * launches per round for all chains (grid: neighbour x chain) and one raster
+ * launch over exactly the neighbours the chains have live in that round (a
+ * compact candidate list written on the device; a chain at high acceptance has
+ * one, a cold chain the round's width, a chain that finished the chunk none).
+ * Chain k draws from the Philox stream of seeds[k] and, without exchange,
+ * follows bit for bit the ggs_sa_create + ggs_sa_run session with that seed on
+ * init_inds[k] and temps[k]: current and best genome, both energies, curves and
+ * the accepted count.  Its trajectory does not depend on K, on the other
+ * chains, on `width`, or on how many rounds are queued between host syncs.
+ * cfg: pop_size = the neighbour capacity PER CHAIN.  Only the ggs_sa_run driver
+ * exists for groups: no propose/commit, explicit draws or incremental evaluation.
+ * Replica exchange (exchange_every = M > 0, shared target only): ggs_sa_chains_run
+ * splits its range after every iteration `it` with (it + 1) % M == 0 (iterations
+ * count absolutely, as passed in); once all chains have finished it, exchange
+ * e = (it + 1) / M - 1 considers the pairs (k, k + 1), k % 2 == e % 2, k + 1 < K,
+ * all from the pre-exchange energies: with T_k chain k's temperature of
+ * iteration `it` and d = (E_k - E_{k+1}) (1 / T_k - 1 / T_{k+1}) in float64, the
+ * pair trades current genome and energy iff u < exp(d),
+ * u = ggs_sa_exchange_uniform(exchange_seed, it, k) (equal temperatures: always;
+ * a pair with a temperature <= 0 is skipped and not counted).  Each chain of a
+ * swapped pair then applies annealing.py:148-150 (curr + 1e-12 < best: that state
+ * becomes its best).  Curves already written are not touched.
+ * K < 1 or K > GGS_SA_MAX_CHAINS, null pointers, exchange_every < 0,
+ * exchange_every > 0 with _create_targets (an energy measured on another image
+ * means nothing) and ggs_sa_run's argument rules are reported (GGS_EINVAL)
+ * before any device is touched. */
+#define GGS_SA_MAX_CHAINS 64
+typedef struct ggs_sa_chains {
+    int32_t n_chains;          /* K >= 1 */
+    int32_t exchange_every;    /* M iterations between replica exchanges, 0 = never */
+    const uint64_t* seeds;     /* [K] Philox seed of each chain (cfg->seed is ignored) */
+    uint64_t exchange_seed;    /* key of the exchange uniforms */
+} ggs_sa_chains;
+/* One target and mask for all chains (ONE target plan); init_fits [K] may be NULL. */
+int ggs_sa_chains_create(int32_t device, const ggs_ga_config* cfg, const ggs_sa_chains* chains,
+                         const float* target_hw3, const float* mask_hw, const float* init_inds /* [K,N,9] */,
+                         void** handle, float* init_fits /* [K] */);
+/* A target per chain: targets_khw3 [K,H,W,3], masks_khw [K,H,W] (NULL iff
+ * fitness_mode is GGS_FIT_NONE), one plan set; chain k anneals image k. */
+int ggs_sa_chains_create_targets(int32_t device, const ggs_ga_config* cfg, const ggs_sa_chains* chains,
+                                 const float* targets_khw3, const float* masks_khw,
+                                 const float* init_inds /* [K,N,9] */, void** handle, float* init_fits /* [K] */);
+/* ggs_sa_run for every chain: temps [K][n_its], curves_out [K][n_its][2]. */
+int ggs_sa_chains_run(void* handle, int32_t first_it, int32_t n_its, int32_t total_iters, int32_t tries,
+                      const double* temps, int32_t width, double* curves_out);
+/* The chains' loop state after the last run, arrays of K (any output may be NULL),
+ * and the session's exchange counts. */
+int ggs_sa_chains_state(void* handle, double* best_fit, double* curr_fit, uint64_t* rounds, uint64_t* evaluated,
+                        uint64_t* accepted, uint64_t* swaps_tried, uint64_t* swaps_accepted);
+/* Synchronises; any output may be NULL: current, best [K,N,9]. */
+int ggs_sa_chains_read(void* handle, float* current, float* best);
+void ggs_sa_chains_destroy(void* handle);
+/* The exchange uniform in [0, 1) of pair (k, k + 1) after iteration it: the Philox
+ * block of ggs_sa_accept_uniform with counter word what = 1. */
+int ggs_sa_exchange_uniform(uint64_t exchange_seed, int32_t it, int32_t k, double* u);
+
 /* ---- multi-GPU fitness gather -------------------------------
  * One process per GPU; candidates are sharded in contiguous blocks and the only
  * exchange is an all-gather of each rank's fitness scalars over RCCL (xGMI).
