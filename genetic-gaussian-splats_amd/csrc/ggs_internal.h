@@ -358,6 +358,34 @@ hipError_t launch_ga_migrate_copy(hipStream_t st, int K, float* pop, const float
 hipError_t launch_ga_migrate_install(hipStream_t st, int K, float* fits, int P, int m, int elite_k, const int* mig,
                                      const float* refit, int* elite);
 
+// ---- differential evolution (ggs_de_*; kernels in ggs_ga.hip) -------------------
+struct DeParamsDev {
+    int strategy;               // 0 rand/1, 1 best/1, 2 current-to-best/1
+    int crossover;              // 0 per gene, 1 per splat
+    float f_lo, f_hi, cr;
+    float log_lo, log_hi;       // clamp_genome scale bounds, as GaParamsDev
+};
+// Trial i of generation gen from pop [P][N][9] (4 <= P <= ga_breed_max_population(),
+// N >= 1): trials [P][N][9] with their raster records recs / bnds [P][N].
+// best_row (device): the row of lowest fitness, written by launch_de_select.
+hipError_t launch_de_variation(hipStream_t st, const float* pop, int P, int N, const DeParamsDev& prm, uint64_t seed,
+                               int gen, const int* best_row, float* trials, SplatRec* recs, int4* bnds, int H, int W,
+                               float k_sigma);
+struct DeSelectDev {
+    float* pop;                 // [P][N][9], rows replaced in place
+    const float* trials;        // [P][N][9]
+    const float* fits;          // [P] the population's fitness
+    const float* trial_fits;    // [P]
+    float* fits_next;           // [P] the new fitness vector (another buffer than fits)
+    int* best_row;
+    double* best_fit;
+    float* best_ind;            // [N][9]
+    double* curves_row;         // [3] best, mean, median
+};
+// One-to-one selection, best so far and the curves row.  init: the statistics of
+// the population as it is (trials, trial_fits and fits_next unused).
+hipError_t launch_de_select(hipStream_t st, const DeSelectDev& d, int P, int N, int init);
+
 // ---- target preparation and importance mask (ggs_mask.hip) ---------------------
 // K images [K][H0][W0][3] -> targets [K][H][W][3] (prepare_target) and, with prm,
 // masks [K][H][W] (compute_importance_mask of each prepared target), enqueued on

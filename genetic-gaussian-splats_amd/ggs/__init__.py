@@ -10,5 +10,6 @@ from .parallel import RcclGather  # noqa: F401
 from .api import (TargetPlan, TargetPlanSet, as_f32, encode, fitness, fitness_device,  # noqa: F401
                   fitness_population, preprocess, profile_enable, profile_read, profile_reset,
                   render, render_device)
+from .de import differential_evolution  # noqa: F401
 
 __version__ = "0.1.0"

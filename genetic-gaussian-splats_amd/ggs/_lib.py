@@ -52,6 +52,12 @@ class GaIslands(C.Structure):
                 ("topology", C.c_int32), ("seeds", C.POINTER(C.c_uint64))]
 
 
+class DeParams(C.Structure):
+    """ggs_de_params (include/ggs.h)."""
+    _fields_ = [("strategy", C.c_int32), ("crossover", C.c_int32), ("f_lo", C.c_float), ("f_hi", C.c_float),
+                ("cr", C.c_float)]
+
+
 class MaskParams(C.Structure):
     """ggs_mask_params (include/ggs.h)."""
     _fields_ = [("n_scales", C.c_int32), ("edge_scales", C.c_int32 * 4), ("w_edge", C.c_float),
@@ -143,6 +149,12 @@ SIGNATURES = {
     # ggs_ga_draws_out is ggs_ga_draws with writable arrays: one ctypes structure serves both
     "ggs_ga_philox_draws": (C.c_int, [C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_float, C.POINTER(GaDraws)]),
+    "ggs_de_create": (C.c_int, [C.c_int32, C.POINTER(GaConfig), C.POINTER(DeParams), _f32p, _f32p, _f32p,
+                                C.POINTER(C.c_void_p)]),
+    "ggs_de_set_params": (C.c_int, [C.c_void_p, C.POINTER(DeParams)]),
+    "ggs_de_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "ggs_de_read": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p, _f64p, _f64p, _i32p]),
+    "ggs_de_destroy": (None, [C.c_void_p]),
     "ggs_comm_unique_id": (C.c_int, [C.c_void_p]),
     "ggs_comm_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                   C.POINTER(C.c_void_p)]),

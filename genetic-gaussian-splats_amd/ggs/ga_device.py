@@ -424,6 +424,81 @@ class DeviceGAIslands:
             pass
 
 
+class DeviceDE:
+    """One device-resident differential-evolution population (ggs_de_* in
+    include/ggs.h; ``ggs.de`` states the algorithm in numpy and names the
+    strategies and crossovers).  ``F``: a number (fixed) or ``(f_lo, f_hi)`` (per
+    trial uniform in that range); ``CR`` in [0, 1].  4 <= P <= 512."""
+
+    def __init__(self, target, mask, init_pop, *, strategy="rand1", crossover="gene", F=(0.5, 0.9),
+                 CR: float = 0.3, min_scale_splats: float, max_scale_splats: float,
+                 k_sigma: float = 3.0, boost_only: bool = False, boost_beta: float = 1.0,
+                 seed: int = 0, device: int = 0):
+        pop = _arr(init_pop, np.float32)
+        if pop.ndim != 3 or pop.shape[2] != 9:
+            raise _lib.GGSInputError("the device DE keeps [P, N, 9] genomes")
+        P, N, _ = pop.shape
+        self.target = _arr(target, np.float32)
+        H, W = self.target.shape[:2]
+        self.mask = None if mask is None else _arr(mask, np.float32)
+        zero = dict.fromkeys(SIG_KEYS, 0.0)             # the GA's operator fields are not read
+        cfg = _config(P, N, H, W, 1, 0, 0.0, 0.0, k_sigma, min_scale_splats, max_scale_splats,
+                      self.mask, boost_only, boost_beta, "linear", zero, zero, seed)
+        self.P, self.N, self.H, self.W = P, N, H, W
+        h = C.c_void_p()
+        # arguments are validated before the library looks for a device
+        check(lib.ggs_de_create(device, C.byref(cfg), C.byref(self._params(strategy, crossover, F, CR)),
+                                self.target.ctypes.data_as(_f32p),
+                                None if self.mask is None else self.mask.ctypes.data_as(_f32p),
+                                pop.ctypes.data_as(_f32p), C.byref(h)), "ggs_de_create")
+        self.h = h
+
+    @staticmethod
+    def _params(strategy, crossover, F, CR) -> "_lib.DeParams":
+        from .de import crossover_id, f_range, strategy_id
+        f_lo, f_hi = f_range(F)
+        return _lib.DeParams(strategy_id(strategy), crossover_id(crossover), f_lo, f_hi, float(CR))
+
+    def set_params(self, *, strategy="rand1", crossover="gene", F=(0.5, 0.9), CR: float = 0.3) -> None:
+        """The operator parameters of the generations run from now on."""
+        check(lib.ggs_de_set_params(self.h, C.byref(self._params(strategy, crossover, F, CR))),
+              "ggs_de_set_params")
+
+    def run(self, first_gen: int, n_gens: int) -> None:
+        check(lib.ggs_de_run(self.h, int(first_gen), int(n_gens)), "ggs_de_run")
+
+    def read(self) -> Dict[str, object]:
+        """``DeviceGA.read``'s dict plus ``trials`` / ``trial_fits`` of the last
+        generation run (unspecified before the first)."""
+        pop = np.empty((self.P, self.N, 9), np.float32)
+        trials = np.empty((self.P, self.N, 9), np.float32)
+        fits, tf = np.empty(self.P, np.float32), np.empty(self.P, np.float32)
+        best = np.empty((self.N, 9), np.float32)
+        bf = C.c_double()
+        n = C.c_int32()
+        check(lib.ggs_de_read(self.h, None, None, None, None, None, None, None, C.byref(n)), "ggs_de_read")
+        curves = np.empty((n.value, 3), np.float64)
+        check(lib.ggs_de_read(self.h, pop.ctypes.data_as(_f32p), fits.ctypes.data_as(_f32p),
+                              trials.ctypes.data_as(_f32p), tf.ctypes.data_as(_f32p),
+                              best.ctypes.data_as(_f32p), C.byref(bf), curves.ctypes.data_as(_f64p),
+                              C.byref(n)), "ggs_de_read")
+        return {"population": pop, "fitness": fits, "trials": trials, "trial_fits": tf, "best": best,
+                "best_fit": bf.value,
+                "curves": {"best": curves[:, 0].tolist(), "mean": curves[:, 1].tolist(),
+                           "median": curves[:, 2].tolist()}}
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            lib.ggs_de_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 — interpreter shutdown
+            pass
+
+
 def draws_from_host(tour_idx, perm, cx, cxu_compact, mut, N: int) -> Dict[str, np.ndarray]:
     """Pack the draws ggs/ga.py's next_generation consumed into the device layout
     (crossover masks expanded to one row per pair)."""

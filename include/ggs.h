@@ -441,6 +441,51 @@ void ggs_sa_chains_destroy(void* handle);
  * block of ggs_sa_accept_uniform with counter word what = 1. */
 int ggs_sa_exchange_uniform(uint64_t exchange_seed, int32_t it, int32_t k, double* u);
 
+/* ---- differential evolution: a third device-resident optimiser ----------------
+ * A population of cfg->pop_size axes-angle genomes evolved by DE on one GPU, three
+ * launches per generation on the session's own stream: variation (P trials with
+ * their raster records), the fitness raster over the P trials, select.  Generation
+ * gen >= 1 is synchronous (every trial is built from the population as it stood
+ * at the start of the generation).  Target row i draws from the Philox block
+ * (gen, i, what, 9) keyed by cfg->seed: three distinct rows r1, r2, r3 != i, a
+ * forced crossover position jrand, F_i = f_lo + u (f_hi - f_lo) and one uniform
+ * per gene (crossover 0) or per splat (crossover 1).  Mutant v (float32, one
+ * rounding per operation, angle differences through wrap_angle):
+ *   strategy 0  rand/1             x[r1] + F (x[r2] - x[r3])
+ *   strategy 1  best/1             x[best] + F (x[r1] - x[r2])
+ *   strategy 2  current-to-best/1  (x[i] + F (x[best] - x[i])) + F (x[r1] - x[r2])
+ * with best the row of lowest fitness (ties: the lowest row).  A gene (all nine
+ * genes of a splat, crossover 1) comes from the mutant iff its uniform < cr or it
+ * is the jrand gene (splat), and is then clamped by clamp_genome's rule of its
+ * column; every other gene is the parent's, bit for bit.  Trial i replaces row i
+ * iff f_trial[i] <= f[i] (float32: a NaN keeps the parent).  Best so far and the
+ * curves follow ggs_ga_*'s arithmetic.  ggs/de.py restates all of it in numpy and
+ * DESIGN.md has the counter layout; a run is held to that restatement bit for bit.
+ * From cfg: pop_size, n_splats, H, W, k_sigma, the scale bounds, fitness_mode,
+ * boost_beta and seed; the rest is ignored.  pop_size < 4 or > 512, n_splats < 1,
+ * cr outside [0, 1], f_lo > f_hi or not finite, an unknown strategy or crossover,
+ * null required pointers and a mask missing for the mode are reported
+ * (GGS_EINVAL) before any device is touched. */
+typedef struct ggs_de_params {
+    int32_t strategy;     /* 0 rand/1, 1 best/1, 2 current-to-best/1 */
+    int32_t crossover;    /* 0 per gene, 1 per splat */
+    float f_lo, f_hi;     /* F per trial uniform in [f_lo, f_hi]; equal = fixed F */
+    float cr;             /* [0, 1] */
+} ggs_de_params;
+/* init_pop [P,N,9] (required); mask may be NULL iff fitness_mode is GGS_FIT_NONE.
+ * Evaluates the initial population (curves row 0). */
+int ggs_de_create(int32_t device, const ggs_ga_config* cfg, const ggs_de_params* de,
+                  const float* target_hw3, const float* mask_hw, const float* init_pop, void** handle);
+/* New parameters for the generations run from now on (F / CR schedules from the host). */
+int ggs_de_set_params(void* handle, const ggs_de_params* de);
+int ggs_de_run(void* handle, int32_t first_gen, int32_t n_gens);
+/* Synchronises; any output may be NULL.  pop, trials [P,N,9]; fits, trial_fits [P];
+ * curves [n_curves][3] = best, mean, median.  trials / trial_fits are those of the
+ * last generation run (unspecified before the first). */
+int ggs_de_read(void* handle, float* pop, float* fits, float* trials, float* trial_fits,
+                float* best_ind, double* best_fit, double* curves, int32_t* n_curves);
+void ggs_de_destroy(void* handle);
+
 /* ---- multi-GPU fitness gather -------------------------------
  * One process per GPU; candidates are sharded in contiguous blocks and the only
  * exchange is an all-gather of each rank's fitness scalars over RCCL (xGMI).
@@ -501,7 +546,8 @@ int ggs_comm_barrier(void* comm);
  * When enabled, every launch of "prep", "raster" and "finalize" is bracketed
  * by hipEvents; ggs_profile_read synchronises those events and returns the
  * accumulated milliseconds and launch count for the named kernel (a finalize
- * folded into the raster counts as raster time, no finalize launch). */
+ * folded into the raster counts as raster time, no finalize launch).  A DE
+ * session's variation counts as "prep" and its select launch as "select". */
 int ggs_profile_enable(int32_t on);
 int ggs_profile_read(const char* kernel, double* total_ms, int64_t* launches);
 void ggs_profile_reset(void);
