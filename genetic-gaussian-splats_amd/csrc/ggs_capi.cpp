@@ -108,6 +108,12 @@ bool fitness_api_fold() {
     const char* v = getenv("GGS_FITNESS_FOLD");
     return v && atoi(v) != 0;
 }
+// A/B and test switch: GGS_STRIP_WORDS=0 keeps the raster's own cull from the bounds
+// where prep would hand it strip words (read per call; the same bits either way).
+bool strip_words_on() {
+    const char* v = getenv("GGS_STRIP_WORDS");
+    return !(v && *v && atoi(v) == 0);
+}
 
 struct PinBuf {
     void* p = nullptr;
@@ -132,6 +138,7 @@ struct Workspace {
     hipStream_t stream = nullptr;
     DevBuf recs, bnds, partials, wpartials, order, plan, fctr;   // fctr: fused-finalize counters
     DevBuf maskws;                    // target preparation / importance mask scratch (ggs_mask.hip)
+    DevBuf swords, smasks;            // strip words and masks, prep -> raster (StripWords)
     int order_H = -1, order_W = -1;   // (H, W) the tile order was built for
     uint64_t plan_key = 0;            // inputs the plan was built from (0: none / volatile)
 };
@@ -236,7 +243,7 @@ void prof_drain_locked() {
 int raster_fitness(hipStream_t st, int simds, const SplatRec* recs, const int4* bnds, int B, int N, int H, int W,
                    const float4* plan, float* partials, const float* wpartials, int mode, const int* order,
                    DevBuf& ctr, float* out, bool fuse, const unsigned char* dirty = nullptr,
-                   const float* clean = nullptr, int group = 0) {
+                   const float* clean = nullptr, int group = 0, const StripWords& sw = StripWords{}) {
     const float bg[3] = {1.f, 1.f, 1.f};  // fitness renders with the default background (fitness.py:15)
     int nTX;
     const int nTiles = raster_tiles(H, W, &nTX);
@@ -261,7 +268,7 @@ int raster_fitness(hipStream_t st, int simds, const SplatRec* recs, const int4* 
     {
         ProfScope ps(st, 1);
         GGS_HIP(launch_raster(st, 1, recs, bnds, B, N, H, W, bg, nullptr, plan, partials, order, dirty, clean,
-                              nullptr, nullptr, simds, group));
+                              nullptr, nullptr, simds, group, sw));
     }
     ProfScope ps(st, 2);
     GGS_HIP(launch_finalize(st, partials, wpartials, B, nTiles, mode, H, W, out, nullptr, group));
@@ -423,6 +430,17 @@ int check_dims(int64_t B, int32_t N, int32_t C, int32_t H, int32_t W) {
 }
 
 // ---- the device pipelines (ctx locked, device set) ----------------------------------
+// The workspace's strip-word buffers for a batch of B x N splats where the batch
+// qualifies and the switch is on (else *sw stays empty: the raster culls from bnds).
+int ensure_strip_words(Workspace* w, int64_t B, int N, int H, int W, hipStream_t st, StripWords* sw) {
+    if (!strip_words_ok(N) || !strip_words_on()) return GGS_OK;
+    int rc;
+    if ((rc = ensure(w->swords, strip_words_bytes(B, N, H, W), st))) return rc;
+    if ((rc = ensure(w->smasks, strip_masks_bytes(B, N, H, W), st))) return rc;
+    sw->words = (int*)w->swords.p;
+    sw->masks = (uint64_t*)w->smasks.p;
+    return GGS_OK;
+}
 int run_fitness_planned(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C,
                         const float4* plan, const float* wpartials, int mode, int H, int W, float k,
                         float* d_out, int group = 0);
@@ -469,13 +487,17 @@ int run_fitness_planned(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B
     if ((rc = ensure(w->partials, sizeof(float) * 4 * (size_t)(B * nTiles), st))) return rc;
     if ((rc = ensure_tile_order(w, H, W, st))) return rc;
     SplatRec* recs = (SplatRec*)w->recs.p;
+    const bool fold = fitness_api_fold();
+    StripWords sw;   // for the single-plan raster without the fold (the instances with visit words)
+    if (group == 0 && !fold && (rc = ensure_strip_words(w, B, N, H, W, st, &sw))) return rc;
     {
         ProfScope ps(st, 0);
-        GGS_HIP(launch_prep(st, true, d_gen, B * N, C, H, W, k, recs, (int4*)w->bnds.p, nullptr, nullptr, nullptr));
+        GGS_HIP(launch_prep(st, true, d_gen, B * N, C, H, W, k, recs, (int4*)w->bnds.p, nullptr, nullptr, nullptr,
+                            nullptr, 0, sw, N));
     }
     return raster_fitness(st, c->simds, recs, (const int4*)w->bnds.p, (int)B, N, H, W, plan, (float*)w->partials.p,
-                          wpartials, mode, (const int*)w->order.p, w->fctr, d_out, fitness_api_fold(), nullptr,
-                          nullptr, group);
+                          wpartials, mode, (const int*)w->order.p, w->fctr, d_out, fold, nullptr,
+                          nullptr, group, sw);
 }
 
 int run_render(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C, int H, int W,
@@ -487,14 +509,17 @@ int run_render(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, 
     if ((rc = ensure(w->bnds, sizeof(int4) * (size_t)std::max<int64_t>(B * N, 1), st))) return rc;
     if ((rc = ensure_tile_order(w, H, W, st))) return rc;
     SplatRec* recs = (SplatRec*)w->recs.p;
+    StripWords sw;
+    if ((rc = ensure_strip_words(w, B, N, H, W, st, &sw))) return rc;
     {
         ProfScope ps(st, 0);
-        GGS_HIP(launch_prep(st, false, d_gen, B * N, C, H, W, k, recs, (int4*)w->bnds.p, nullptr, nullptr, nullptr));
+        GGS_HIP(launch_prep(st, false, d_gen, B * N, C, H, W, k, recs, (int4*)w->bnds.p, nullptr, nullptr, nullptr,
+                            nullptr, 0, sw, N));
     }
     {
         ProfScope ps(st, 1);
         GGS_HIP(launch_raster(st, 0, recs, (const int4*)w->bnds.p, (int)B, N, H, W, bg, d_img, nullptr, nullptr,
-                              (const int*)w->order.p, nullptr, nullptr, nullptr, nullptr, c->simds));
+                              (const int*)w->order.p, nullptr, nullptr, nullptr, nullptr, c->simds, 0, sw));
     }
     return GGS_OK;
 }
@@ -590,7 +615,8 @@ void ggs_shutdown(void) {
         (void)hipStreamSynchronize(c->stream);
         for (auto& w : c->ws) {
             if (w->stream) (void)hipStreamSynchronize(w->stream);
-            for (DevBuf* b : {&w->recs, &w->bnds, &w->partials, &w->wpartials, &w->order, &w->plan, &w->fctr, &w->maskws})
+            for (DevBuf* b : {&w->recs, &w->bnds, &w->partials, &w->wpartials, &w->order, &w->plan, &w->fctr, &w->maskws,
+                              &w->swords, &w->smasks})
                 if (b->p) (void)hipFree(b->p);
         }
         for (DevBuf* b : {&c->gen, &c->out, &c->target, &c->mask, &c->prep_in, &c->prep_tgt, &c->prep_mask})

@@ -49,9 +49,23 @@ static_assert(sizeof(SplatRec) == 64, "SplatRec must be 64 bytes");
 // live (the device SA loop sizes its grids for the session's capacity and sets the
 // round's neighbour count on the device); the other threads / waves exit at once.
 // recs [S] and bnds [S] (the records' AABBs, compact for the raster's cull) go together.
+// Strip words (optional): with both buffers set, N splats per candidate (S = B * N)
+// and strip_words_ok(N), prep also makes the raster's integer cull tests, once per
+// candidate (words [B][nTY][N], masks: see prep_strip_words), and a launch_raster of
+// the same batch that is handed the same buffers only compacts its strip lists from
+// them: the same lists, so the same bits.  Anything else (null buffers, other N, a
+// live count, dirty strips, the saturation and folded-finalize instances) culls
+// from bnds as before.
+struct StripWords {
+    int* words = nullptr;         // strip_words_bytes
+    uint64_t* masks = nullptr;    // strip_masks_bytes
+};
+bool strip_words_ok(int N);       // N % 64 == 0 and at most the no-saturation-check limit
+size_t strip_words_bytes(int64_t B, int N, int H, int W);
+size_t strip_masks_bytes(int64_t B, int N, int H, int W);
 hipError_t launch_prep(hipStream_t st, bool encode, const float* genomes, int64_t S, int C, int H,
                        int W, float k, SplatRec* recs, int4* bnds, float* f9, int* i4, float* enc9,
-                       const int* live = nullptr, int n_per = 0);
+                       const int* live = nullptr, int n_per = 0, const StripWords& sw = StripWords{}, int N = 0);
 int raster_tiles(int H, int W, int* nTX);
 // The fitness finalize folded into the raster (MODE 1): each strip wave counts
 // itself in ctr[b] after storing its partial, and the candidate's last strip
@@ -76,7 +90,7 @@ hipError_t launch_raster(hipStream_t st, int mode, const SplatRec* recs, const i
                          const float bg[3], float* img, const float4* plan, float* partials,
                          const int* tile_order, const unsigned char* dirty = nullptr,
                          const float* clean = nullptr, const int* live = nullptr, const FinFused* fin = nullptr,
-                         int simds = 0, int group = 0);
+                         int simds = 0, int group = 0, const StripWords& sw = StripWords{});
 // SIMDs (CUs x 4) of HIP device `dev`, 0 if unknown.
 int device_simds(int dev);
 

@@ -61,12 +61,19 @@ using namespace detmath;
 // finalize 269 us from dispatch to end); a lone 44-VGPR wave fits any slot a strip
 // wave frees (17.7 / 5.7 us; headline +0.9 %, docs/EXPERIMENTS.md §19).
 constexpr int PREP_THREADS = 64;
+// the strip words and masks of one 64-splat block (defined beside visit_word)
+__device__ __forceinline__ void prep_strip_words(int N, int H, int W, const int4& bb,
+                                                 int* __restrict__ swords, uint64_t* __restrict__ smasks);
 template <bool ENCODE>
 __global__ void __launch_bounds__(PREP_THREADS)
 prep_kernel(const float* __restrict__ genomes, int64_t S, int C, int H, int W, float k,
             SplatRec* __restrict__ recs, int4* __restrict__ bnds, float* __restrict__ f9, int* __restrict__ i4,
-            float* __restrict__ enc9, const int* __restrict__ live, int n_per) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+            float* __restrict__ enc9, const int* __restrict__ live, int n_per,
+            int* __restrict__ swords, uint64_t* __restrict__ smasks, int N) {
+    // with strip masks (S % 64 == 0, no live count: launch_prep) a block takes its 64
+    // splats in descending order, the order of the raster's cull lanes, so a ballot
+    // over the block is a cull chunk's mask as it stands
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + (smasks ? 63 - (int)threadIdx.x : (int)threadIdx.x);
     if (i >= S) return;
     if (live && i >= (int64_t)*live * n_per) return;   // SA loop: candidates past the round's count
     const float* g = genomes + i * (int64_t)C;
@@ -86,6 +93,7 @@ prep_kernel(const float* __restrict__ genomes, int64_t S, int C, int H, int W, f
         const SplatRec r = make_rec(p);
         recs[i] = r;
         bnds[i] = rec_bounds(r);
+        if (smasks) prep_strip_words(N, H, W, rec_bounds(r), swords, smasks);
     }
     if (f9) {
         f9[0 * S + i] = p.cx;  f9[1 * S + i] = p.cy;  f9[2 * S + i] = p.sxx;
@@ -186,14 +194,78 @@ __device__ __forceinline__ int ufirst(int v) { return __builtin_amdgcn_readfirst
 // (2048^2 SA: +1.5 %, the longer cull pays the words) keep plain byte offsets
 // (docs/EXPERIMENTS.md §16).
 constexpr unsigned VW_ABOVE = 32u, VW_KA = 26, VW_CLIP = 31, VW_OFFSET = 0x03FFFFC0u;
-__device__ __forceinline__ int visit_word(int i, const int4& bb, int ty0, int sx0) {
+// The word has two encoders, the cull below and prep (prep_strip_words): its row
+// half depends on (splat, row tile) only, its clip bit on (splat, column strip) only.
+__device__ __forceinline__ int visit_row_word(int i, const int4& bb, int ty0) {
     constexpr int NP = GGS_TILE_H / 8;
+    static_assert(NP == NPK, "kB counts the raster's packed row pairs");
+    static_assert(NPK < 32, "kB (0..NPK) lies below VW_ABOVE");
     const int dy0 = bb.z - ty0, dy1 = bb.w - ty0;
     const unsigned kA = (unsigned)max(dy0, 0) >> 3;
     const unsigned kB = dy1 >= GGS_TILE_H - 1 ? (unsigned)NP : (unsigned)dy1 >> 3;
     const unsigned above = dy0 <= 0 ? VW_ABOVE : 0u;
-    const unsigned clip = max(bb.x - sx0, sx0 + 15 - bb.y) > 0 ? (1u << VW_CLIP) : 0u;
-    return (int)(((unsigned)i << 6) | kB | above | (kA << VW_KA) | clip);
+    return (int)(((unsigned)i << 6) | kB | above | (kA << VW_KA));
+}
+__device__ __forceinline__ bool strip_clips(const int4& bb, int sx0) { return max(bb.x - sx0, sx0 + 15 - bb.y) > 0; }
+__device__ __forceinline__ int visit_word(int i, const int4& bb, int ty0, int sx0) {
+    return visit_row_word(i, bb, ty0) | (int)(strip_clips(bb, sx0) ? 1u << VW_CLIP : 0u);
+}
+static_assert(SAT_MIN_SPLATS * sizeof(SplatRec) <= VW_OFFSET + 64, "a record offset fits the word's offset field");
+
+// Strip words: the cull's integer tests done once per candidate in prep instead of
+// once per strip wave (a candidate's nTiles * 4 strip waves all test the same N
+// bounds).  The tests are separable: a splat hits a strip iff it hits the strip's
+// 16 columns and the tile's rows; the word's row half is per (splat, row tile), its
+// clip bit per (splat, column strip).  Per candidate, N % 64 == 0, N <= SAT_MIN_SPLATS:
+//   swords [B][nTY][N]       visit_row_word of splat i against row tile ty
+//   smasks [B][R][ncp] u64   R = 2 nCS + nTY rows of cull-chunk masks, nCS = 4 nTX
+//                            column strips: rows [0, nCS) "hits the strip's columns",
+//                            [nCS, 2 nCS) "the AABB cuts the strip's columns",
+//                            [2 nCS, R) "hits the row tile's rows"; strips that
+//                            start at or past W get zero masks.
+// Chunk c, bit L of a mask is splat N - 1 - 64 c - L, the cull's lane order; ncp is
+// N / 64 rounded up to 4 (the raster loads four chunks' masks at a time; the
+// padding is never written and never used).
+__host__ __device__ constexpr int strip_mask_chunks(int N) { return ((N >> 6) + 3) & ~3; }
+__device__ __forceinline__ void prep_strip_words(int N, int H, int W, const int4& bb,
+                                                 int* __restrict__ swords, uint64_t* __restrict__ smasks) {
+    const int lane = threadIdx.x;
+    // the block's candidate and first splat (uniform; launch_prep: S fits 32 bits)
+    const int first = (int)(blockIdx.x * 64u), b = first / N, s = first - b * N + 63 - lane;
+    const int nTY = (H + TILE_H - 1) / TILE_H, nCS = (W + TILE - 1) / TILE * 4, R = 2 * nCS + nTY;
+    const int ncp = strip_mask_chunks(N);
+    for (int ty = 0; ty < nTY; ++ty) swords[((int64_t)b * nTY + ty) * N + s] = visit_row_word(s, bb, ty * TILE_H);
+    // A block's 64 lanes are one cull chunk (uniform), a ballot over them is one mask word.
+    // The column tests as strip ranges (floor division by 16, exact for any integers):
+    // x1 >= sx0 && x0 <= sx0 + 15 is lo <= cs <= hi, and the AABB does not cut the strip,
+    // x0 <= sx0 && x1 >= sx0 + 15, is flo <= cs <= fhi.  Lane j collects strip c0 + j's two
+    // words, 64 strips go out in one store per kind; strips from nW on, which
+    // start at or past W, keep zero masks.
+    uint64_t* __restrict__ mcol = smasks + (int64_t)b * R * ncp + ((N >> 6) - 1 - (s >> 6));
+    const int lo = bb.x >> 4, hi = bb.y >> 4, flo = (bb.x + 15) >> 4, fhi = ((bb.y + 1) >> 4) - 1;
+    const int nW = (W + 15) >> 4;
+    for (int c0 = 0; c0 < nCS; c0 += 64) {
+        uint64_t mh = 0, mk = 0;
+        const int n = min(64, nW - c0);
+#pragma unroll 4
+        for (int j = 0; j < n; ++j) {
+            const int cs = c0 + j;
+            const uint64_t h = __builtin_amdgcn_ballot_w64((lo <= cs) & (cs <= hi));
+            const uint64_t k = __builtin_amdgcn_ballot_w64((cs < flo) | (cs > fhi));
+            const bool me = lane == j;
+            mh = me ? h : mh;
+            mk = me ? k : mk;
+        }
+        if (c0 + lane < nCS) {
+            mcol[(int64_t)(c0 + lane) * ncp] = mh;
+            mcol[(int64_t)(nCS + c0 + lane) * ncp] = mk;
+        }
+    }
+    for (int ty = 0; ty < nTY; ++ty) {
+        const int ty0 = ty * TILE_H, ty1 = min(ty0 + TILE_H, H) - 1;
+        const uint64_t m = __builtin_amdgcn_ballot_w64((bb.w >= ty0) & (bb.z <= ty1));
+        if (lane == 0) mcol[(int64_t)(2 * nCS + ty) * ncp] = m;
+    }
 }
 
 // One strip's partial (lane 0).  With the fused finalize: an agent-scope store,
@@ -350,7 +422,7 @@ __device__ __forceinline__ f2_t fma2(f2_t a, f2_t b, f2_t c) { return __builtin_
 // raster_body is the one kernel body; its entry points are raster_kernel (one
 // target plan per launch) and raster_multi_kernel (a plan set: candidate b is
 // scored against plan b / group, MULTI).
-template <int MODE, bool SAT, bool FUSED, bool MULTI, bool LIST = false>
+template <int MODE, bool SAT, bool FUSED, bool MULTI, bool LIST = false, bool PRE = false>
 __device__ __forceinline__ void
 raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, int B, int N, int H, int W, int nTX,
             int nTiles,
@@ -358,7 +430,8 @@ raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, in
             const float4* __restrict__ plan, float* __restrict__ partials,
             const int* __restrict__ tile_order, const unsigned char* __restrict__ dirty,
             const float* __restrict__ clean, const int* __restrict__ live, int CH, FinFused fin, int simds,
-            int group, const int* __restrict__ plan_of = nullptr) {
+            int group, const int* __restrict__ plan_of = nullptr, const int* __restrict__ swords = nullptr,
+            const uint64_t* __restrict__ smasks = nullptr) {
     static_assert(!MULTI || MODE == 1, "plan sets are for the fitness epilogue");
     static_assert(!LIST || MULTI, "a plan list names plans of a plan set");
     constexpr bool DS = GGS_DEPTH_SPLIT && MODE == 1 && !SAT;
@@ -498,11 +571,19 @@ raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, in
 #endif
     constexpr int AHEAD = SAT ? GGS_SAT_AHEAD : GGS_CULL_AHEAD;
     static_assert(AHEAD >= 1 && AHEAD <= 4, "cull prefetch depth");
+    // strip words (prep_strip_words): prep has made the cull's tests, the wave only
+    // compacts its list.  A template twin, not a runtime test: with both culls in one
+    // instance the fitness kernel spilled 4 SGPRs (the plan pointer and the lane-0 mask)
+    static_assert(!PRE || (VW && !DS), "strip words are visit words");
+    constexpr bool pre = PRE;
     // issued in chunk order (sched barriers), so each chunk waits vmcnt(AHEAD - 1)
-    int4 bbA = bounds(GGS_NHI - 1 - lane), bbB, bbC, bbD;
-    if constexpr (AHEAD > 1) { __builtin_amdgcn_sched_barrier(0); bbB = bounds(GGS_NHI - 1 - lane - 64); }
-    if constexpr (AHEAD > 2) { __builtin_amdgcn_sched_barrier(0); bbC = bounds(GGS_NHI - 1 - lane - 128); }
-    if constexpr (AHEAD > 3) { __builtin_amdgcn_sched_barrier(0); bbD = bounds(GGS_NHI - 1 - lane - 192); }
+    int4 bbA = {}, bbB = {}, bbC = {}, bbD = {};
+    if constexpr (!pre) {
+        bbA = bounds(GGS_NHI - 1 - lane);
+        if constexpr (AHEAD > 1) { __builtin_amdgcn_sched_barrier(0); bbB = bounds(GGS_NHI - 1 - lane - 64); }
+        if constexpr (AHEAD > 2) { __builtin_amdgcn_sched_barrier(0); bbC = bounds(GGS_NHI - 1 - lane - 128); }
+        if constexpr (AHEAD > 3) { __builtin_amdgcn_sched_barrier(0); bbD = bounds(GGS_NHI - 1 - lane - 192); }
+    }
     int base = 0;                     // first splat (from the back) not yet culled
     // a batch is handed to the blend once it holds more than LIMIT splats; a step
     // adds at most 64 * AHEAD, so the list (CAP) cannot overflow
@@ -534,7 +615,52 @@ raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, in
             cnt += __popcll(m);                                                             \
             base += 64;                                                                     \
         }
-        if constexpr (AHEAD == 1) {
+        if constexpr (pre) {
+            // every load of the cull goes out at the wave's start: per step of four
+            // chunks one row word per lane and chunk, and, on the scalar side, the
+            // strip's column-hit, column-clip and row-hit masks.  The list is word
+            // for word the one the tests below write: the hit set is the same, the
+            // prefix runs over the lower lanes (higher splat indices), and the word
+            // is prep's row half with the clip bit from the clip mask.  One batch:
+            // N <= SAT_MIN_SPLATS <= LIMIT.
+            static_assert(SAT_MIN_SPLATS <= LIMIT, "strip words: the whole cull is one batch");
+            const int nch = N >> 6, ncp = strip_mask_chunks(N), nTY = (H + TILE_H - 1) / TILE_H, nCS = nTX * 4;
+            const int ty = t / nTX;
+            const int* __restrict__ rw = swords + ((int64_t)b * nTY + ty) * N;
+            const uint64_t* __restrict__ mhit = smasks + ((int64_t)b * (2 * nCS + nTY) + (sx0 >> 4)) * ncp;
+            const uint64_t* __restrict__ mclip = mhit + (int64_t)nCS * ncp;
+            const uint64_t* __restrict__ mrow = mhit + (int64_t)(2 * nCS + ty - (sx0 >> 4)) * ncp;
+            for (int c0 = 0; c0 < nch; c0 += 4) {
+                const int i0 = N - 1 - 64 * c0 - lane;      // chunks past N: a clamped load, an empty mask
+                int w0 = rw[i0], w1 = rw[max(i0 - 64, 0)], w2 = rw[max(i0 - 128, 0)], w3 = rw[max(i0 - 192, 0)];
+                uint64_t a0 = mhit[c0], a1 = mhit[c0 + 1], a2 = mhit[c0 + 2], a3 = mhit[c0 + 3];
+                uint64_t r0 = mrow[c0], r1 = mrow[c0 + 1], r2 = mrow[c0 + 2], r3 = mrow[c0 + 3];
+                uint64_t k0 = mclip[c0], k1 = mclip[c0 + 1], k2 = mclip[c0 + 2], k3 = mclip[c0 + 3];
+                // every load is issued, and waited for once, here: left alone the compiler
+                // sinks a chunk's word load into its branch and issues the third mask load
+                // behind the wait for the first two, one latency after the other
+                asm volatile("" : "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3), "+s"(a0), "+s"(a1), "+s"(a2), "+s"(a3),
+                                  "+s"(r0), "+s"(r1), "+s"(r2), "+s"(r3), "+s"(k0), "+s"(k1), "+s"(k2), "+s"(k3));
+                const uint64_t h0 = a0 & r0;
+                const uint64_t h1 = a1 & r1 & (c0 + 1 < nch ? ~0ull : 0ull);
+                const uint64_t h2 = a2 & r2 & (c0 + 2 < nch ? ~0ull : 0ull);
+                const uint64_t h3 = a3 & r3 & (c0 + 3 < nch ? ~0ull : 0ull);
+#define GGS_LIST_CHUNK(WD, HM, KM)                                                              \
+                {                                                                           \
+                    if (__builtin_amdgcn_inverse_ballot_w64(HM))                            \
+                        list[cnt + (int)__builtin_amdgcn_mbcnt_hi((unsigned)((HM) >> 32),   \
+                                        __builtin_amdgcn_mbcnt_lo((unsigned)(HM), 0u))] =   \
+                            __builtin_amdgcn_inverse_ballot_w64(KM) ? (WD) | (int)(1u << VW_CLIP) : (WD); \
+                    cnt += __popcll(HM);                                                    \
+                }
+                GGS_LIST_CHUNK(w0, h0, k0)
+                GGS_LIST_CHUNK(w1, h1, k1)
+                GGS_LIST_CHUNK(w2, h2, k2)
+                GGS_LIST_CHUNK(w3, h3, k3)
+#undef GGS_LIST_CHUNK
+            }
+            base = N;
+        } else if constexpr (AHEAD == 1) {
             GGS_CULL_CHUNK(bbA)
             if (cnt <= LIMIT && base < GGS_NR) continue;
         } else {
@@ -991,9 +1117,30 @@ raster_kernel(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, 
               float bg_r, float bg_g, float bg_b, float* __restrict__ img,
               const float4* __restrict__ plan, float* __restrict__ partials,
               const int* __restrict__ tile_order, const unsigned char* __restrict__ dirty,
-              const float* __restrict__ clean, const int* __restrict__ live, int CH, FinFused fin, int simds) {
-    raster_body<MODE, SAT, FUSED, false>(recs, bnds, B, N, H, W, nTX, nTiles, bg_r, bg_g, bg_b, img, plan, partials,
-                                         tile_order, dirty, clean, live, CH, fin, simds, 1);
+              const float* __restrict__ clean, const int* __restrict__ live, int CH, FinFused fin, int simds,
+              const int* __restrict__ swords, const uint64_t* __restrict__ smasks) {
+    // the instances with visit words compact prep's strip words (launch_raster hands
+    // batches without them to bounds_cull_kernel)
+    constexpr bool PRE = !SAT && !FUSED && !GGS_DEPTH_SPLIT;
+    raster_body<MODE, SAT, FUSED, false, false, PRE>(recs, bnds, B, N, H, W, nTX, nTiles, bg_r, bg_g, bg_b, img, plan,
+                                                     partials, tile_order, dirty, clean, live, CH, fin, simds, 1,
+                                                     nullptr, swords, smasks);
+}
+
+// raster_kernel<MODE, false, false> with the cull of its own from the bounds, for
+// the launches prep wrote no strip words for: N % 64 != 0, records from the fused
+// variation / mutation kernels, a live count, dirty strips, GGS_STRIP_WORDS=0.
+// (Named without the body's name: the resource tests count the entry points by it;
+// tests/test_kernel_resources_strip_words.py holds these two to the same budget.)
+template <int MODE>
+__global__ void __launch_bounds__(GGS_DEPTH_SPLIT ? 2 * NT : NT, OCC)
+bounds_cull_kernel(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, int B, int N, int H, int W,
+                   int nTX, int nTiles, float bg_r, float bg_g, float bg_b, float* __restrict__ img,
+                   const float4* __restrict__ plan, float* __restrict__ partials,
+                   const int* __restrict__ tile_order, const unsigned char* __restrict__ dirty,
+                   const float* __restrict__ clean, const int* __restrict__ live, int CH, int simds) {
+    raster_body<MODE, false, false, false>(recs, bnds, B, N, H, W, nTX, nTiles, bg_r, bg_g, bg_b, img, plan, partials,
+                                           tile_order, dirty, clean, live, CH, FinFused{}, simds, 1);
 }
 
 // The fitness raster against a plan set: `plan` and fin.wpartials are those of
@@ -1226,16 +1373,20 @@ hipError_t launch_detmath(hipStream_t st, const float* x, const float* y, int64_
 // ---------------------------------------------------------------------------
 hipError_t launch_prep(hipStream_t st, bool encode, const float* genomes, int64_t S, int C, int H,
                        int W, float k, SplatRec* recs, int4* bnds, float* f9, int* i4, float* enc9, const int* live,
-                       int n_per) {
+                       int n_per, const StripWords& sw, int N) {
     if (S <= 0) return hipSuccess;
+    // strip words: whole 64-splat blocks of one candidate, every thread present
+    const bool strips = sw.masks && sw.words && recs && !live && strip_words_ok(N) && S % N == 0 && S < ((int64_t)1 << 31);
+    int* const swords = strips ? sw.words : nullptr;
+    uint64_t* const smasks = strips ? sw.masks : nullptr;
     constexpr int PB = PREP_THREADS;  // (round 3's "64-thread blocks: no change" was one stream, nothing competing)
     const unsigned grid = (unsigned)((S + PB - 1) / PB);
     if (encode)
         hipLaunchKernelGGL(prep_kernel<true>, dim3(grid), dim3(PB), 0, st, genomes, S, C, H, W, k,
-                           recs, bnds, f9, i4, enc9, live, n_per);
+                           recs, bnds, f9, i4, enc9, live, n_per, swords, smasks, N);
     else
         hipLaunchKernelGGL(prep_kernel<false>, dim3(grid), dim3(PB), 0, st, genomes, S, C, H, W, k,
-                           recs, bnds, f9, i4, enc9, live, n_per);
+                           recs, bnds, f9, i4, enc9, live, n_per, swords, smasks, N);
     return hipGetLastError();
 }
 
@@ -1259,6 +1410,15 @@ void raster_tile_order(int H, int W, int* order) {
 }
 
 int raster_order_len(int H, int W) { return raster_tiles(H, W, nullptr) * SPB; }
+
+bool strip_words_ok(int N) { return N > 0 && N <= SAT_MIN_SPLATS && N % 64 == 0; }
+size_t strip_words_bytes(int64_t B, int N, int H, int W) {
+    return sizeof(int) * (size_t)B * (size_t)((H + TILE_H - 1) / TILE_H) * (size_t)N;
+}
+size_t strip_masks_bytes(int64_t B, int N, int H, int W) {
+    const size_t rows = 2 * (size_t)((W + TILE - 1) / TILE) * 4 + (size_t)((H + TILE_H - 1) / TILE_H);
+    return sizeof(uint64_t) * (size_t)B * rows * (size_t)strip_mask_chunks(N);
+}
 
 int raster_tiles(int H, int W, int* nTX) {
     const int tx = (W + TILE - 1) / TILE, ty = (H + TILE_H - 1) / TILE_H;
@@ -1292,7 +1452,7 @@ int device_simds(int dev) {
 hipError_t launch_raster(hipStream_t st, int mode, const SplatRec* recs, const int4* bnds, int B, int N, int H, int W,
                          const float bg[3], float* img, const float4* plan, float* partials,
                          const int* tile_order, const unsigned char* dirty, const float* clean,
-                         const int* live, const FinFused* fin, int simds, int group) {
+                         const int* live, const FinFused* fin, int simds, int group, const StripWords& sw) {
     int nTX;
     const int nTiles = raster_tiles(H, W, &nTX);
     const dim3 grid((unsigned)((int64_t)B * nTiles * SPB)), block(NT);
@@ -1301,24 +1461,36 @@ hipError_t launch_raster(hipStream_t st, int mode, const SplatRec* recs, const i
     const int CH = raster_chunk(N);
     const FinFused ff = (mode != 0 && fin) ? *fin : FinFused{};
     if (GGS_DEPTH_SPLIT) simds = 0;
+    // strip words written by the launch's prep (launch_prep): whole batches only
+    const bool strips = !GGS_DEPTH_SPLIT && sw.masks && sw.words && !live && !dirty && strip_words_ok(N);
+    const int* const swords = strips ? sw.words : nullptr;
+    const uint64_t* const smasks = strips ? sw.masks : nullptr;
     // FUSED is a template parameter, so the instances without the fold carry none
     // of its code (a runtime test left the SA raster 1 % slower than round 3's)
 #define GGS_RASTER(M, S, F)                                                                    \
     hipLaunchKernelGGL((raster_kernel<M, S, F>), grid, (M) ? block_f : block, 0, st, recs, bnds, B, N, H, W, nTX, nTiles, \
-                       bg[0], bg[1], bg[2], img, plan, partials, tile_order, dirty, clean, live, CH, ff, simds)
+                       bg[0], bg[1], bg[2], img, plan, partials, tile_order, dirty, clean, live, CH, ff, simds, swords, smasks)
     // the saturation check only where strip lists can grow long (N > SAT_MIN_SPLATS);
     // at the bench's 256 splats the kernel without it is the faster code (+1.6 %)
 #define GGS_RASTER_MULTI(S, F)                                                                 \
     hipLaunchKernelGGL((raster_multi_kernel<S, F>), grid, block_f, 0, st, recs, bnds, B, N, H, W, nTX, nTiles, bg[0], \
                        bg[1], bg[2], plan, partials, tile_order, CH, ff, simds, group)
+    // the instances with visit words: raster_kernel takes prep's strip words, its twin culls from the bounds
+#define GGS_BOUNDS_CULL(M)                                                                     \
+    hipLaunchKernelGGL((bounds_cull_kernel<M>), grid, (M) ? block_f : block, 0, st, recs, bnds, B, N, H, W, nTX, nTiles, \
+                       bg[0], bg[1], bg[2], img, plan, partials, tile_order, dirty, clean, live, CH, simds)
     if (group > 0) {   // a plan set: the separately named entry points, fitness only
         if (mode != 1 || dirty || clean || live) return hipErrorInvalidValue;
         if (!ff.ctr) { if (!sat) GGS_RASTER_MULTI(false, false); else GGS_RASTER_MULTI(true, false); }
         else { if (!sat) GGS_RASTER_MULTI(false, true); else GGS_RASTER_MULTI(true, true); }
     }
-    else if (mode == 0) { if (!sat) GGS_RASTER(0, false, false); else GGS_RASTER(0, true, false); }   // image
-    else if (!ff.ctr) { if (!sat) GGS_RASTER(1, false, false); else GGS_RASTER(1, true, false); }   // fitness
+    else if (mode == 0) {                                                                         // image
+        if (sat) GGS_RASTER(0, true, false); else if (strips) GGS_RASTER(0, false, false); else GGS_BOUNDS_CULL(0);
+    } else if (!ff.ctr) {                                                                         // fitness
+        if (sat) GGS_RASTER(1, true, false); else if (strips) GGS_RASTER(1, false, false); else GGS_BOUNDS_CULL(1);
+    }
     else { if (!sat) GGS_RASTER(1, false, true); else GGS_RASTER(1, true, true); }  // + folded finalize
+#undef GGS_BOUNDS_CULL
 #undef GGS_RASTER_MULTI
 #undef GGS_RASTER
     return hipGetLastError();
