@@ -139,6 +139,7 @@ struct Workspace {
     DevBuf recs, bnds, partials, wpartials, order, plan, fctr;   // fctr: fused-finalize counters
     DevBuf maskws;                    // target preparation / importance mask scratch (ggs_mask.hip)
     DevBuf swords, smasks;            // strip words and masks, prep -> raster (StripWords)
+    DevBuf gf9, gi4, gpart, gout;     // fitness gradient: prep's stage outputs, strip partials, unwanted fitness
     int order_H = -1, order_W = -1;   // (H, W) the tile order was built for
     uint64_t plan_key = 0;            // inputs the plan was built from (0: none / volatile)
 };
@@ -176,7 +177,7 @@ struct DevCtx {
     std::mutex mu;
     std::vector<std::unique_ptr<Workspace>> ws;
     // host-API staging
-    DevBuf gen, out, target, mask;
+    DevBuf gen, out, target, mask, ggrad;   // ggrad: ggs_fitness_grad's [B,N,9]
     DevBuf prep_in, prep_tgt, prep_mask;   // ggs_targets_prepare / ggs_quantiles staging
     PinBuf h_out;                  // the fitness scalars (render and genomes go straight to / from the caller)
     uint64_t target_key = 0, mask_key = 0;
@@ -524,6 +525,54 @@ int run_render(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, 
     return GGS_OK;
 }
 
+// The strip partials of the gradient in flight per launch: candidates are chunked
+// to this budget (the raster's chunk policy, 40 MiB), and one candidate above it
+// is refused rather than given a second layout.
+constexpr size_t kGradChunkBytes = (size_t)40 << 20;
+
+// Argument errors (GGS_EINVAL) and the workspace budget (GGS_ENOMEM), before any device is touched.
+int check_grad_dims(int64_t B, int32_t N, int32_t C, int32_t H, int32_t W, int32_t mode, const void* mask) {
+    if (B < 1 || N < 1) return fail(GGS_EINVAL, "B=%lld and N=%d must be >= 1", (long long)B, N);
+    int rc = check_dims(B, N, C, H, W);
+    if (rc) return rc;
+    if (mode < GGS_FIT_NONE || mode > GGS_FIT_BOOST) return fail(GGS_EINVAL, "bad fitness mode %d", mode);
+    if (mode != GGS_FIT_NONE && !mask) return fail(GGS_EINVAL, "mode %d needs a weight mask", mode);
+    if (B * N >= (int64_t)1 << 31) return fail(GGS_EINVAL, "B*N = %lld splats exceeds the limit; split the batch",
+                                               (long long)(B * N));
+    const size_t per = grad_partial_bytes(N, H, W);
+    if (per > kGradChunkBytes)
+        return fail(GGS_ENOMEM, "the gradient's strip partials of one candidate (%d x %d, %d splats: %.0f MB) exceed "
+                                "the %.0f MB workspace budget", H, W, N, per / 1048576.0, kGradChunkBytes / 1048576.0);
+    return GGS_OK;
+}
+
+// Fitness (the existing prep -> raster -> finalize path, so ggs_fitness_device's
+// bits) and its gradient [B][N][9].  d_out may be null.
+int run_fitness_grad(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C, const float* d_target,
+                     const float* d_mask, int mode, float beta, int H, int W, float k, float* d_out, float* d_grad,
+                     uint64_t plan_key = 0) {
+    Workspace* w = workspace_for(c, st);
+    const size_t per = grad_partial_bytes(N, H, W);     // within the budget: check_grad_dims
+    int rc;
+    if (!d_out) {
+        if ((rc = ensure(w->gout, sizeof(float) * (size_t)B, st))) return rc;
+        d_out = (float*)w->gout.p;
+    }
+    // first: it leaves the plan's weight block (the mode's Sum w) in the workspace
+    if ((rc = run_fitness(c, st, d_gen, B, N, C, d_target, d_mask, mode, beta, H, W, k, d_out, plan_key))) return rc;
+    const int64_t S = B * N;
+    const int chunk = (int)std::min<int64_t>(B, (int64_t)(kGradChunkBytes / per));
+    if ((rc = ensure(w->gf9, sizeof(float) * 9 * (size_t)S, st))) return rc;
+    if ((rc = ensure(w->gi4, sizeof(int) * 4 * (size_t)S, st))) return rc;
+    if ((rc = ensure(w->gpart, per * (size_t)chunk, st))) return rc;
+    GGS_HIP(launch_prep(st, true, d_gen, S, C, H, W, k, nullptr, nullptr, (float*)w->gf9.p, (int*)w->gi4.p, nullptr));
+    for (int64_t b0 = 0; b0 < B; b0 += chunk)
+        GGS_HIP(launch_grad(st, d_gen, C, (const float*)w->gf9.p, (const int*)w->gi4.p, B, b0,
+                            (int)std::min<int64_t>(chunk, B - b0), N, H, W, d_target, d_mask, mode, beta,
+                            (const float*)w->wpartials.p, w->gpart.p, d_grad));
+    return GGS_OK;
+}
+
 // Split [0, B) into n contiguous shards of ceil(B/n) (the last ones shorter or
 // empty): equal-sized slots, so the fitness shards meet in one in-place RCCL
 // all-gather (ggs/parallel.py shard_bounds: the same rule).
@@ -616,10 +665,10 @@ void ggs_shutdown(void) {
         for (auto& w : c->ws) {
             if (w->stream) (void)hipStreamSynchronize(w->stream);
             for (DevBuf* b : {&w->recs, &w->bnds, &w->partials, &w->wpartials, &w->order, &w->plan, &w->fctr, &w->maskws,
-                              &w->swords, &w->smasks})
+                              &w->swords, &w->smasks, &w->gf9, &w->gi4, &w->gpart, &w->gout})
                 if (b->p) (void)hipFree(b->p);
         }
-        for (DevBuf* b : {&c->gen, &c->out, &c->target, &c->mask, &c->prep_in, &c->prep_tgt, &c->prep_mask})
+        for (DevBuf* b : {&c->gen, &c->out, &c->target, &c->mask, &c->ggrad, &c->prep_in, &c->prep_tgt, &c->prep_mask})
             if (b->p) (void)hipFree(b->p);
         for (PinBuf* b : {&c->h_out})
             if (b->p) (void)hipHostFree(b->p);
@@ -645,6 +694,20 @@ int ggs_fitness_device(int32_t device, void* stream, const float* d_genomes_axes
     DeviceGuard dg(c->dev);
     return run_fitness(c, (hipStream_t)stream, d_genomes_axes, B, N, C, d_target_hw3, d_mask_hw, mode,
                        boost_beta, H, W, k_sigma, d_out_B);
+}
+
+int ggs_fitness_grad_device(int32_t device, void* stream, const float* d_genomes_axes, int64_t B, int32_t N,
+                            int32_t C, const float* d_target_hw3, const float* d_mask_hw, int32_t mode,
+                            float boost_beta, int32_t H, int32_t W, float k_sigma, float* d_out_B, float* d_grad_BN9) {
+    int rc = check_grad_dims(B, N, C, H, W, mode, d_mask_hw);
+    if (rc) return rc;
+    if (!d_genomes_axes || !d_target_hw3 || !d_grad_BN9) return fail(GGS_EINVAL, "null genomes/target/grad");
+    DevCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    return run_fitness_grad(c, (hipStream_t)stream, d_genomes_axes, B, N, C, d_target_hw3, d_mask_hw, mode, boost_beta,
+                            H, W, k_sigma, d_out_B, d_grad_BN9);
 }
 
 // ---- target plans (device API with a target prepared once) ------------------
@@ -1083,6 +1146,50 @@ int ggs_fitness(const float* genomes_axes, int64_t B, int32_t N, int32_t C, cons
     if ((rc = drain.drain())) return rc;
     memcpy(out_B, cs[0]->h_out.p, sizeof(float) * B);
     return GGS_OK;
+}
+
+int ggs_fitness_grad(const float* genomes_axes, int64_t B, int32_t N, int32_t C, const float* target_hw3,
+                     const float* mask_hw, int32_t mode, float boost_beta, int32_t H, int32_t W, float k_sigma,
+                     float* out_B, float* grad_BN9) {
+    int rc = check_grad_dims(B, N, C, H, W, mode, mask_hw);
+    if (rc) return rc;
+    if (!genomes_axes || !target_hw3 || !out_B || !grad_BN9) return fail(GGS_EINVAL, "null pointer");
+    std::vector<DevCtx*> cs;
+    if ((rc = active_ctxs(1, &cs))) return rc;
+    DevCtx* c = cs[0];
+    const size_t tbytes = sizeof(float) * 3 * (size_t)H * W, mbytes = sizeof(float) * (size_t)H * W;
+    const size_t gbytes = sizeof(float) * (size_t)N * C * (size_t)B, dbytes = sizeof(float) * 9 * (size_t)N * (size_t)B;
+    const uint64_t tkey = hash_bytes(target_hw3, tbytes);
+    const uint64_t mkey = mask_hw ? hash_bytes(mask_hw, mbytes) : 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    hipStream_t st = c->stream;
+    StreamDrain drain;                  // after the context lock: drained on every return
+    if ((rc = ensure(c->out, sizeof(float) * (size_t)B, st)) || (rc = ensure(c->ggrad, dbytes, st)) ||
+        (rc = ensure(c->target, tbytes, st)) || (mask_hw && (rc = ensure(c->mask, mbytes, st))) ||
+        (rc = ensure(c->gen, gbytes, st)))
+        return rc;
+    GGS_HIP(hipStreamSynchronize(st));  // the previous call's work is done with c->gen
+    drain.add(c->dev, st);
+    if (tkey != c->target_key || tbytes != c->target_bytes) {
+        GGS_HIP(hipMemcpyAsync(c->target.p, target_hw3, tbytes, hipMemcpyHostToDevice, st));
+        c->target_key = tkey;
+        c->target_bytes = tbytes;
+    }
+    if (mask_hw && (mkey != c->mask_key || mbytes != c->mask_bytes)) {
+        GGS_HIP(hipMemcpyAsync(c->mask.p, mask_hw, mbytes, hipMemcpyHostToDevice, st));
+        c->mask_key = mkey;
+        c->mask_bytes = mbytes;
+    }
+    GGS_HIP(hipMemcpyAsync(c->gen.p, genomes_axes, gbytes, hipMemcpyHostToDevice, st));
+    if ((rc = run_fitness_grad(c, st, (const float*)c->gen.p, B, N, C, (const float*)c->target.p,
+                               mask_hw ? (const float*)c->mask.p : nullptr, mode, boost_beta, H, W, k_sigma,
+                               (float*)c->out.p, (float*)c->ggrad.p, host_plan_key(tkey, mkey, boost_beta, mode, H, W))))
+        return rc;
+    GGS_HIP(hipMemcpyAsync(out_B, c->out.p, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st));
+    GGS_HIP(hipMemcpyAsync(grad_BN9, c->ggrad.p, dbytes, hipMemcpyDeviceToHost, st));
+    if (inject_fail_after(1)) return fail(GGS_EHIP, "injected failure after device 1's work (test hook)");
+    return drain.drain();
 }
 
 int ggs_render(const float* genomes, int64_t B, int32_t N, int32_t C, int32_t H, int32_t W,
@@ -3076,6 +3183,181 @@ void ggs_de_destroy(void* handle) {
         DeviceGuard dg(s->c->dev);
         if (s->st) (void)hipStreamSynchronize(s->st);
         de_free(s);
+    }
+    delete s;
+}
+
+}  // extern "C"
+
+// ---- Adam refiner (ggs_refine_*) ---------------------------------------------------
+namespace ggs {
+namespace {
+
+// B candidates refined side by side on the session's own stream: per step one
+// gradient call (fitness and gradient of the state x_t), the best-so-far update
+// (x_t, its fitness) and one elementwise Adam update.  The pipeline buffers are the
+// stream's pooled workspace, dropped with the session.
+struct RefineSession {
+    DevCtx* c = nullptr;
+    hipStream_t st = nullptr;
+    ggs_ga_config cfg{};
+    ggs_refine_params prm{};
+    int B = 0, N = 0;
+    int64_t t = 0;                 // Adam steps taken
+    uint64_t plan_key = 0;         // the session's target never changes
+    DevBuf x, m, v, grad, fits, best_x, best_fit, target, mask;
+};
+
+std::atomic<uint64_t> g_refine_serial{1};
+
+void refine_free(RefineSession* s) {
+    for (DevBuf* b : {&s->x, &s->m, &s->v, &s->grad, &s->fits, &s->best_x, &s->best_fit, &s->target, &s->mask})
+        if (b->p) (void)hipFree(b->p);
+    if (s->st) {
+        // the stream's workspace goes with it (a later stream may get the same handle)
+        for (auto it = s->c->ws.begin(); it != s->c->ws.end(); ++it)
+            if ((*it)->stream == s->st) {
+                Workspace* w = it->get();
+                for (DevBuf* b : {&w->recs, &w->bnds, &w->partials, &w->wpartials, &w->order, &w->plan, &w->fctr,
+                                  &w->maskws, &w->swords, &w->smasks, &w->gf9, &w->gi4, &w->gpart, &w->gout})
+                    if (b->p) (void)hipFree(b->p);
+                s->c->ws.erase(it);
+                break;
+            }
+        (void)hipStreamDestroy(s->st);
+    }
+}
+
+int refine_check_params(const ggs_refine_params* p) {
+    if (!p) return fail(GGS_EINVAL, "null ggs_refine_params");
+    for (int c = 0; c < 9; ++c)
+        if (!std::isfinite(p->lr[c]) || p->lr[c] < 0.0f) return fail(GGS_EINVAL, "lr[%d]=%g must be finite and >= 0", c, p->lr[c]);
+    if (!(p->beta1 >= 0.0f && p->beta1 < 1.0f)) return fail(GGS_EINVAL, "beta1=%g must be in [0, 1)", p->beta1);
+    if (!(p->beta2 >= 0.0f && p->beta2 < 1.0f)) return fail(GGS_EINVAL, "beta2=%g must be in [0, 1)", p->beta2);
+    if (!(p->eps > 0.0f) || !std::isfinite(p->eps)) return fail(GGS_EINVAL, "eps=%g must be > 0", p->eps);
+    return GGS_OK;
+}
+
+// fitness (and, with grad, the gradient) of the current state into s->fits
+int refine_eval(RefineSession* s, bool grad) {
+    const ggs_ga_config& c = s->cfg;
+    const float* d_mask = s->mask.p ? (const float*)s->mask.p : nullptr;
+    if (grad)
+        return run_fitness_grad(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, (const float*)s->target.p, d_mask,
+                                c.fitness_mode, c.boost_beta, c.H, c.W, c.k_sigma, (float*)s->fits.p,
+                                (float*)s->grad.p, s->plan_key);
+    return run_fitness(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, (const float*)s->target.p, d_mask,
+                       c.fitness_mode, c.boost_beta, c.H, c.W, c.k_sigma, (float*)s->fits.p, s->plan_key);
+}
+
+}  // namespace
+}  // namespace ggs
+
+extern "C" {
+
+int ggs_refine_create(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p, const float* target_hw3,
+                      const float* mask_hw, const float* genomes_BN9, int32_t B, void** handle) {
+    if (!cfg || !p || !target_hw3 || !genomes_BN9 || !handle) return fail(GGS_EINVAL, "null argument");
+    const ggs_ga_config& c = *cfg;
+    int rc = check_grad_dims(B, c.n_splats, 9, c.H, c.W, c.fitness_mode, mask_hw);
+    if (rc) return rc;
+    if ((rc = refine_check_params(p))) return rc;
+    DevCtx* ctx = nullptr;
+    if ((rc = get_ctx(device, &ctx))) return rc;
+    auto s = std::make_unique<RefineSession>();
+    s->c = ctx;
+    s->cfg = c;
+    s->prm = *p;
+    ga_fill_log_bounds(&s->cfg);
+    s->B = B;
+    s->N = c.n_splats;
+    s->plan_key = (1ull << 63) | g_refine_serial.fetch_add(1);     // host_plan_key never sets bit 63
+    const size_t pb = sizeof(float) * 9 * (size_t)B * s->N, hw = (size_t)c.H * c.W;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard dg(ctx->dev);
+    auto bail = [&](int code) { refine_free(s.get()); return code; };
+    if (hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess)
+        return bail(fail(GGS_EHIP, "stream creation failed"));
+    if ((rc = ensure(s->x, pb, s->st)) || (rc = ensure(s->m, pb, s->st)) || (rc = ensure(s->v, pb, s->st)) ||
+        (rc = ensure(s->grad, pb, s->st)) || (rc = ensure(s->best_x, pb, s->st)) ||
+        (rc = ensure(s->fits, sizeof(float) * (size_t)B, s->st)) ||
+        (rc = ensure(s->best_fit, sizeof(double) * (size_t)B, s->st)) ||
+        (rc = ensure(s->target, sizeof(float) * 3 * hw, s->st)) ||
+        (mask_hw && (rc = ensure(s->mask, sizeof(float) * hw, s->st))))
+        return bail(rc);
+    std::vector<double> inf((size_t)B, (double)INFINITY);
+    if (hipMemcpyAsync(s->target.p, target_hw3, sizeof(float) * 3 * hw, hipMemcpyHostToDevice, s->st) ||
+        (mask_hw && hipMemcpyAsync(s->mask.p, mask_hw, sizeof(float) * hw, hipMemcpyHostToDevice, s->st)) ||
+        hipMemcpyAsync(s->x.p, genomes_BN9, pb, hipMemcpyHostToDevice, s->st) ||
+        hipMemcpyAsync(s->best_x.p, genomes_BN9, pb, hipMemcpyHostToDevice, s->st) ||
+        hipMemcpyAsync(s->best_fit.p, inf.data(), sizeof(double) * (size_t)B, hipMemcpyHostToDevice, s->st) ||
+        hipMemsetAsync(s->m.p, 0, pb, s->st) || hipMemsetAsync(s->v.p, 0, pb, s->st) ||
+        hipMemsetAsync(s->grad.p, 0, pb, s->st))
+        return bail(fail(GGS_EHIP, "upload failed"));
+    if (hipStreamSynchronize(s->st) != hipSuccess)     // the caller's arrays may be freed on return
+        return bail(fail(GGS_EHIP, "upload failed"));
+    *handle = s.release();
+    return GGS_OK;
+}
+
+int ggs_refine_run(void* handle, int32_t n_steps) {
+    if (!handle || n_steps < 0) return fail(GGS_EINVAL, "bad arguments");
+    RefineSession* s = (RefineSession*)handle;
+    std::lock_guard<std::mutex> lk(s->c->mu);
+    DeviceGuard dg(s->c->dev);
+    for (int i = 0; i < n_steps; ++i) {
+        int rc;
+        if ((rc = refine_eval(s, true))) return rc;
+        GGS_HIP(launch_refine_best(s->st, (const float*)s->x.p, (const float*)s->fits.p, s->B, s->N,
+                                   (double*)s->best_fit.p, (float*)s->best_x.p));
+        s->t += 1;
+        RefineStepDev p;
+        for (int c = 0; c < 9; ++c) p.lr[c] = s->prm.lr[c];
+        p.beta1 = s->prm.beta1;
+        p.beta2 = s->prm.beta2;
+        p.eps = s->prm.eps;
+        p.c1 = (float)(1.0 - pow((double)s->prm.beta1, (double)s->t));
+        p.c2 = (float)(1.0 - pow((double)s->prm.beta2, (double)s->t));
+        p.log_lo = s->cfg.scale_log_lo;
+        p.log_hi = s->cfg.scale_log_hi;
+        GGS_HIP(launch_refine_adam(s->st, (float*)s->x.p, (float*)s->m.p, (float*)s->v.p, (const float*)s->grad.p,
+                                   s->B, s->N, p));
+    }
+    return GGS_OK;
+}
+
+int ggs_refine_read(void* handle, float* genomes, float* fits, float* best, float* best_fits, float* last_grad) {
+    if (!handle) return fail(GGS_EINVAL, "null handle");
+    RefineSession* s = (RefineSession*)handle;
+    std::lock_guard<std::mutex> lk(s->c->mu);
+    DeviceGuard dg(s->c->dev);
+    // the current state's own fitness, which may also be the best so far
+    int rc;
+    if ((rc = refine_eval(s, false))) return rc;
+    GGS_HIP(launch_refine_best(s->st, (const float*)s->x.p, (const float*)s->fits.p, s->B, s->N,
+                               (double*)s->best_fit.p, (float*)s->best_x.p));
+    GGS_HIP(hipStreamSynchronize(s->st));
+    const size_t pb = sizeof(float) * 9 * (size_t)s->B * s->N;
+    if (genomes) GGS_HIP(hipMemcpy(genomes, s->x.p, pb, hipMemcpyDeviceToHost));
+    if (fits) GGS_HIP(hipMemcpy(fits, s->fits.p, sizeof(float) * (size_t)s->B, hipMemcpyDeviceToHost));
+    if (best) GGS_HIP(hipMemcpy(best, s->best_x.p, pb, hipMemcpyDeviceToHost));
+    if (best_fits) {
+        std::vector<double> bf((size_t)s->B);
+        GGS_HIP(hipMemcpy(bf.data(), s->best_fit.p, sizeof(double) * (size_t)s->B, hipMemcpyDeviceToHost));
+        for (int b = 0; b < s->B; ++b) best_fits[b] = (float)bf[b];   // float32 fitness values, widened: exact
+    }
+    if (last_grad) GGS_HIP(hipMemcpy(last_grad, s->grad.p, pb, hipMemcpyDeviceToHost));
+    return GGS_OK;
+}
+
+void ggs_refine_destroy(void* handle) {
+    if (!handle) return;
+    RefineSession* s = (RefineSession*)handle;
+    {
+        std::lock_guard<std::mutex> lk(s->c->mu);
+        DeviceGuard dg(s->c->dev);
+        if (s->st) (void)hipStreamSynchronize(s->st);
+        refine_free(s);
     }
     delete s;
 }

@@ -415,6 +415,30 @@ size_t quantile_ws_bytes(int A, int nq);
 hipError_t launch_quantiles(hipStream_t st, const float* x, int A, int64_t n, const double* q, int nq, void* ws,
                             float* d_out);
 
+// ---- fitness gradients and the Adam refiner (ggs_grad.hip) -----------------------
+// d fitness / d genome [B][N][9].  f9 / i4: launch_prep's stage outputs of the whole
+// batch (S = B * N columns); the call handles candidates b0 .. b0+nb-1 of it, with
+// partials of nb * grad_partial_bytes (one wave per candidate and 16 x 32 pixel
+// strip writes nine sums per splat it visits, padded to 48 B).  target [H][W][3]
+// and mask [H][W] (or null) as the caller passed them; wblock: the target plan's
+// weight block (launch_plan), whose leading double is the mode's Sum w.
+int grad_strips(int H, int W, int* nSX);
+size_t grad_partial_bytes(int N, int H, int W);
+hipError_t launch_grad(hipStream_t st, const float* genomes, int C, const float* f9, const int* i4, int64_t B,
+                       int64_t b0, int nb, int N, int H, int W, const float* target, const float* mask, int mode,
+                       float beta, const float* wblock, void* partials, float* grad);
+struct RefineStepDev {          // one Adam step's constants (ggs/refine.py adam_step)
+    float lr[9];
+    float beta1, beta2, eps;
+    float c1, c2;               // 1 - beta1^t, 1 - beta2^t: float64 on the host, rounded once
+    float log_lo, log_hi;       // clamp_genome scale bounds, as GaParamsDev
+};
+// x [B][N][9] becomes best_x / best_fit [B] where fits[b] + 1e-10 < best_fit[b] (float64).
+hipError_t launch_refine_best(hipStream_t st, const float* x, const float* fits, int B, int N, double* best_fit,
+                              float* best_x);
+hipError_t launch_refine_adam(hipStream_t st, float* x, float* m, float* v, const float* g, int B, int N,
+                              const RefineStepDev& p);
+
 // ---- RCCL (ggs_comm.cpp) ----------------------------------------------------
 // Grouped in-place all-gather over single-process communicators (ggs_comm_init_local):
 // buf[d] holds shard d at buf[d] + d*per; afterwards every buf[d] holds all n shards.

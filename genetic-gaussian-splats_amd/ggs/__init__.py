@@ -8,8 +8,8 @@ from ._lib import (GGS_FIT_BOOST, GGS_FIT_NONE, GGS_FIT_WEIGHTED, GGSDeviceError
                    GGSError, GGSInputError, LIB_PATH, ensure_init, lib, runtime_info, select_devices)
 from .parallel import RcclGather  # noqa: F401
 from .api import (TargetPlan, TargetPlanSet, as_f32, encode, fitness, fitness_device,  # noqa: F401
-                  fitness_population, preprocess, profile_enable, profile_read, profile_reset,
-                  render, render_device)
+                  fitness_grad, fitness_grad_device, fitness_population, preprocess, profile_enable,
+                  profile_read, profile_reset, render, render_device)
 from .de import differential_evolution  # noqa: F401
 
 __version__ = "0.1.0"

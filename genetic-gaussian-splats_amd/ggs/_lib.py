@@ -58,6 +58,11 @@ class DeParams(C.Structure):
                 ("cr", C.c_float)]
 
 
+class RefineParams(C.Structure):
+    """ggs_refine_params (include/ggs.h)."""
+    _fields_ = [("lr", C.c_float * 9), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float)]
+
+
 class MaskParams(C.Structure):
     """ggs_mask_params (include/ggs.h)."""
     _fields_ = [("n_scales", C.c_int32), ("edge_scales", C.c_int32 * 4), ("w_edge", C.c_float),
@@ -155,6 +160,16 @@ SIGNATURES = {
     "ggs_de_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "ggs_de_read": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p, _f64p, _f64p, _i32p]),
     "ggs_de_destroy": (None, [C.c_void_p]),
+    "ggs_fitness_grad": (C.c_int, [_f32p, C.c_int64, C.c_int32, C.c_int32, _f32p, _f32p, C.c_int32,
+                                   C.c_float, C.c_int32, C.c_int32, C.c_float, _f32p, _f32p]),
+    "ggs_fitness_grad_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
+                                          C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "ggs_refine_create": (C.c_int, [C.c_int32, C.POINTER(GaConfig), C.POINTER(RefineParams), _f32p, _f32p, _f32p,
+                                    C.c_int32, C.POINTER(C.c_void_p)]),
+    "ggs_refine_run": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ggs_refine_read": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "ggs_refine_destroy": (None, [C.c_void_p]),
     "ggs_comm_unique_id": (C.c_int, [C.c_void_p]),
     "ggs_comm_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                   C.POINTER(C.c_void_p)]),

@@ -143,6 +143,34 @@ def fitness(genomes_axes, target, H: int, W: int, k_sigma: float = 3.0,
     return out
 
 
+def fitness_grad(genomes_axes, target, H: int, W: int, k_sigma: float = 3.0,
+                 weight_mask=None, boost_only: bool = False, boost_beta: float = 1.0,
+                 device=None):
+    """``fitness`` and its gradient with respect to the nine axes-angle genes of
+    every splat → (fit float32 [B], grad float32 [B,N,9]); DESIGN.md §8c has the
+    conventions.  ``fit`` has the bits ``fitness`` returns.  One device."""
+    g = _genomes3d(genomes_axes, "fitness_grad")
+    B, N, Cc = g.shape
+    H, W = int(H), int(W)
+    tgt = as_f32(target)
+    if tgt.shape != (H, W, 3):
+        raise GGSInputError(f"target must be [H,W,3] = {(H, W, 3)}, got {tuple(tgt.shape)}")
+    if weight_mask is None:
+        mode, mask_p = _lib.GGS_FIT_NONE, None
+    else:
+        mask = as_f32(weight_mask)
+        if mask.shape != (H, W):
+            raise GGSInputError(f"weight_mask must be [H,W] = {(H, W)}, got {tuple(mask.shape)}")
+        mode = _lib.GGS_FIT_BOOST if boost_only else _lib.GGS_FIT_WEIGHTED
+        mask_p = _fp(mask)
+    out = np.empty((B,), np.float32)
+    grad = np.empty((B, N, 9), np.float32)
+    with _on_devices(device, 1):
+        check(lib.ggs_fitness_grad(_fp(g), B, N, Cc, _fp(tgt), mask_p, mode, float(boost_beta), H, W,
+                                   float(k_sigma), _fp(out), _fp(grad)), "ggs_fitness_grad")
+    return out, grad
+
+
 def encode(G_axes) -> np.ndarray:
     """encode.py:62-79 genome_to_renderer_batched (any leading shape, C ≥ 9) → [..., 9]."""
     g = as_f32(G_axes)
@@ -202,6 +230,16 @@ def fitness_device(device: int, stream: int, d_genomes: int, B: int, N: int, Cc:
                                  C.c_void_p(d_target), C.c_void_p(d_mask or None), mode,
                                  float(boost_beta), H, W, float(k_sigma), C.c_void_p(d_out)),
           "ggs_fitness_device")
+
+
+def fitness_grad_device(device: int, stream: int, d_genomes: int, B: int, N: int, Cc: int,
+                        d_target: int, d_mask: int, mode: int, boost_beta: float, H: int, W: int,
+                        k_sigma: float, d_out: int, d_grad: int) -> None:
+    """Enqueue fitness (d_out [B], may be 0) and gradient (d_grad [B,N,9]) on `stream`."""
+    check(lib.ggs_fitness_grad_device(device, C.c_void_p(stream), C.c_void_p(d_genomes), B, N, Cc,
+                                      C.c_void_p(d_target), C.c_void_p(d_mask or None), mode,
+                                      float(boost_beta), H, W, float(k_sigma), C.c_void_p(d_out or None),
+                                      C.c_void_p(d_grad)), "ggs_fitness_grad_device")
 
 
 class TargetPlan:

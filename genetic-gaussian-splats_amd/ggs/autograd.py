@@ -1,0 +1,77 @@
+"""torch.autograd bridge: the splat fitness as a differentiable function.
+
+``splat_fitness(genomes, target, mask)`` returns the fitness [B] of [B,N,C]
+axes-angle genomes; ``.backward()`` leaves d fitness / d genomes in
+``genomes.grad`` (columns 9.. of a wider genome get zeros).  On HIP tensors the
+device entry point (ggs_fitness_grad_device) runs on torch's current stream with
+no host copy; CPU tensors go through the host-pointer call.  The gradient is
+computed with the fitness in ``forward`` and only scaled in ``backward``.
+
+torch is imported here, never by ``import ggs``.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib, api
+
+
+def _mode(mask, boost_only: bool) -> int:
+    if mask is None:
+        return _lib.GGS_FIT_NONE
+    return _lib.GGS_FIT_BOOST if boost_only else _lib.GGS_FIT_WEIGHTED
+
+
+class SplatFitness(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, genomes, target, mask, k_sigma, boost_only, boost_beta):
+        if genomes.dim() != 3 or genomes.shape[2] < 9:
+            raise _lib.GGSInputError(f"genomes must be [B,N,C>=9], got {tuple(genomes.shape)}")
+        if target.dim() != 3 or target.shape[2] != 3:
+            raise _lib.GGSInputError(f"target must be [H,W,3], got {tuple(target.shape)}")
+        B, N, Cc = genomes.shape
+        H, W = int(target.shape[0]), int(target.shape[1])
+        if mask is not None and tuple(mask.shape) != (H, W):
+            raise _lib.GGSInputError(f"mask must be [H,W] = {(H, W)}, got {tuple(mask.shape)}")
+        if genomes.is_cuda:
+            dev = genomes.device
+            g = genomes.detach().to(torch.float32).contiguous()
+            t = target.detach().to(device=dev, dtype=torch.float32).contiguous()
+            m = None if mask is None else mask.detach().to(device=dev, dtype=torch.float32).contiguous()
+            fit = torch.empty(B, dtype=torch.float32, device=dev)
+            grad9 = torch.empty((B, N, 9), dtype=torch.float32, device=dev)
+            _lib.ensure_init()
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                api.fitness_grad_device(dev.index or 0, stream, g.data_ptr(), B, N, Cc, t.data_ptr(),
+                                        0 if m is None else m.data_ptr(), _mode(m, boost_only), boost_beta,
+                                        H, W, k_sigma, fit.data_ptr(), grad9.data_ptr())
+        else:
+            f, g9 = api.fitness_grad(genomes.detach(), target.detach(), H, W, k_sigma,
+                                     weight_mask=None if mask is None else mask.detach(),
+                                     boost_only=boost_only, boost_beta=boost_beta)
+            fit, grad9 = torch.from_numpy(f), torch.from_numpy(g9)
+        if Cc > 9:
+            grad = torch.zeros((B, N, Cc), dtype=torch.float32, device=grad9.device)
+            grad[:, :, :9] = grad9
+        else:
+            grad = grad9
+        ctx.save_for_backward(grad)
+        ctx.in_dtype = genomes.dtype
+        return fit.to(genomes.dtype) if genomes.dtype != torch.float32 else fit
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (grad,) = ctx.saved_tensors
+        g = grad * grad_output.to(grad.dtype)[:, None, None]
+        return g.to(ctx.in_dtype), None, None, None, None, None
+
+
+def splat_fitness(genomes, target, mask=None, *, k_sigma: float = 3.0, boost_only: bool = False,
+                  boost_beta: float = 1.0):
+    """Fitness [B] of [B,N,C] (or [N,C]: then a scalar) axes-angle genomes, differentiable
+    with respect to ``genomes`` (DESIGN.md §8c names the derivative's conventions)."""
+    if genomes.dim() == 2:
+        return SplatFitness.apply(genomes[None], target, mask, float(k_sigma), bool(boost_only),
+                                  float(boost_beta))[0]
+    return SplatFitness.apply(genomes, target, mask, float(k_sigma), bool(boost_only), float(boost_beta))

@@ -408,8 +408,14 @@ def genetic_approx(target_img_uint8, H: int, W: int, device, pop_size: int, n_sp
                    evaluate: Optional[Callable[[np.ndarray], np.ndarray]] = None,
                    init_population: Optional[np.ndarray] = None, progress: bool = True,
                    return_state: bool = False, backend: str = "auto", chunk: int = 50,
-                   islands: int = 1, migrate_every: int = 0, migrants: int = 0):
+                   islands: int = 1, migrate_every: int = 0, migrants: int = 0,
+                   polish_steps: int = 0):
     """algorithm.py:17-195 → (best individual [N, 9] float32, best fitness).
+
+    ``polish_steps`` > 0: after the last generation the best individual is refined
+    by that many Adam steps on the device gradient (``ggs.refine.refine`` with its
+    default rates, same target, mask and mode) and the refined individual is
+    returned if its fitness is lower.  0 (the default) changes nothing.
 
     Extra keyword-only hooks: ``seed`` / ``draws`` (draw source), ``evaluate``
     (population [M,N,9] → fitness [M]: the initial population, then the P -
@@ -434,6 +440,38 @@ def genetic_approx(target_img_uint8, H: int, W: int, device, pop_size: int, n_sp
     ``return_state`` then also holds ``"islands"``: the per-island ``population``
     [K, P, N, 9], ``fitness`` [K, P] and ``curves`` (a list of K dicts), while
     ``"population"`` / ``"fitness"`` are those of the best island."""
+    out = _genetic_approx_search(target_img_uint8, H, W, device, pop_size, n_splats, generations, tour_k,
+                                 elite_k, cxpb, mutpb, mut_sigma_max, mut_sigma_min, schedule,
+                                 min_scale_splats, max_scale_splats, k_sigma, mask_strength, boost_only,
+                                 save_video, frame_every, video_dir, prefix, loss_png_path, loss_csv_path,
+                                 loss_log_y, seed=seed, draws=draws, evaluate=evaluate,
+                                 init_population=init_population, progress=progress,
+                                 return_state=return_state, backend=backend, chunk=chunk, islands=islands,
+                                 migrate_every=migrate_every, migrants=migrants)
+    if int(polish_steps) <= 0:
+        return out
+    from . import api
+    from .mask import compute_importance_mask, prepare_target
+    from .refine import refine
+    t = prepare_target(target_img_uint8, H, W)
+    imp_mask = compute_importance_mask(t, H, W, edge_scales=(1, 2, 4), w_edge=0.7, w_var=0.3,
+                                       gamma=0.7, floor=0.15, smooth=3, strength=mask_strength)
+    best_ind, best_fit = out[0], out[1]
+    r = refine(best_ind, t, H, W, int(polish_steps), k_sigma=k_sigma, weight_mask=imp_mask,
+               boost_only=boost_only, min_scale_splats=min_scale_splats,
+               max_scale_splats=max_scale_splats, device=api.device_index(device))
+    if float(r["best_fits"][0]) < float(best_fit):
+        best_ind, best_fit = r["best"][0].copy(), float(r["best_fits"][0])
+    return (best_ind, best_fit) + tuple(out[2:])
+
+
+def _genetic_approx_search(target_img_uint8, H, W, device, pop_size, n_splats, generations, tour_k, elite_k,
+                           cxpb, mutpb, mut_sigma_max, mut_sigma_min, schedule, min_scale_splats,
+                           max_scale_splats, k_sigma, mask_strength, boost_only, save_video, frame_every,
+                           video_dir, prefix, loss_png_path, loss_csv_path, loss_log_y, *, seed, draws,
+                           evaluate, init_population, progress, return_state, backend, chunk, islands,
+                           migrate_every, migrants):
+    """``genetic_approx`` without the polish."""
     from .mask import compute_importance_mask, prepare_target
 
     islands = int(islands)

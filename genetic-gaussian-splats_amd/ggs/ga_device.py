@@ -499,6 +499,64 @@ class DeviceDE:
             pass
 
 
+class DeviceRefine:
+    """B candidates refined by Adam on the device (ggs_refine_* in include/ggs.h;
+    ``ggs.refine.adam_step`` states the update in numpy).  ``lr``: nine per-column
+    rates."""
+
+    def __init__(self, target, mask, genomes, *, lr, beta1: float = 0.9, beta2: float = 0.999,
+                 eps: float = 1e-8, min_scale_splats: float, max_scale_splats: float,
+                 k_sigma: float = 3.0, boost_only: bool = False, boost_beta: float = 1.0, device: int = 0):
+        x = _arr(genomes, np.float32)
+        if x.ndim == 2:
+            x = x[None]
+        if x.ndim != 3 or x.shape[2] != 9:
+            raise _lib.GGSInputError("the device refiner keeps [B, N, 9] genomes")
+        B, N, _ = x.shape
+        self.target = _arr(target, np.float32)
+        H, W = self.target.shape[:2]
+        self.mask = None if mask is None else _arr(mask, np.float32)
+        zero = dict.fromkeys(SIG_KEYS, 0.0)             # the GA's operator fields are not read
+        cfg = _config(max(B, 1), N, H, W, 1, 0, 0.0, 0.0, k_sigma, min_scale_splats, max_scale_splats,
+                      self.mask, boost_only, boost_beta, "linear", zero, zero, 0)
+        lr = np.asarray(lr, np.float32).reshape(-1)
+        if lr.shape != (9,):
+            raise _lib.GGSInputError("lr must have nine entries, one per genome column")
+        prm = _lib.RefineParams((C.c_float * 9)(*[float(v) for v in lr]), float(beta1), float(beta2), float(eps))
+        self.B, self.N, self.H, self.W = B, N, H, W
+        h = C.c_void_p()
+        # arguments are validated before the library looks for a device
+        check(lib.ggs_refine_create(device, C.byref(cfg), C.byref(prm), self.target.ctypes.data_as(_f32p),
+                                    None if self.mask is None else self.mask.ctypes.data_as(_f32p),
+                                    x.ctypes.data_as(_f32p), B, C.byref(h)), "ggs_refine_create")
+        self.h = h
+
+    def run(self, n_steps: int) -> None:
+        check(lib.ggs_refine_run(self.h, int(n_steps)), "ggs_refine_run")
+
+    def read(self) -> Dict[str, np.ndarray]:
+        """The current state with its fitness, the best so far per candidate and the
+        gradient of the last step run (zeros before the first)."""
+        shape = (self.B, self.N, 9)
+        x, best, grad = (np.empty(shape, np.float32) for _ in range(3))
+        fits, bf = np.empty(self.B, np.float32), np.empty(self.B, np.float32)
+        check(lib.ggs_refine_read(self.h, x.ctypes.data_as(_f32p), fits.ctypes.data_as(_f32p),
+                                  best.ctypes.data_as(_f32p), bf.ctypes.data_as(_f32p),
+                                  grad.ctypes.data_as(_f32p)), "ggs_refine_read")
+        return {"genomes": x, "fitness": fits, "best": best, "best_fits": bf, "last_grad": grad}
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            lib.ggs_refine_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 — interpreter shutdown
+            pass
+
+
 def draws_from_host(tour_idx, perm, cx, cxu_compact, mut, N: int) -> Dict[str, np.ndarray]:
     """Pack the draws ggs/ga.py's next_generation consumed into the device layout
     (crossover masks expanded to one row per pair)."""

@@ -486,6 +486,56 @@ int ggs_de_read(void* handle, float* pop, float* fits, float* trials, float* tri
                 float* best_ind, double* best_fit, double* curves, int32_t* n_curves);
 void ggs_de_destroy(void* handle);
 
+/* ---- fitness gradients ----------------------------------------
+ * out [B]: the fitness, by the same prep -> raster -> finalize launches as
+ * ggs_fitness_device (the same bits).  grad [B,N,9], whatever the input stride
+ * C >= 9: d out[b] / d genomes[b,s,0:9], the derivative of the composition encode
+ * (encode.py:4-59) -> preprocess (render.py:8-47) -> "over" blend in ascending
+ * splat order (render.py:189-196) -> clip to [0,1] -> fitness.py:7-31, with the
+ * integer AABB held constant, clip(x, lo, hi) passing the gradient iff
+ * lo <= x <= hi and max(x, eps) iff x > eps.  Deterministic: reruns and other
+ * batches give a candidate the same bits.  One device.  B, N, H or W < 1, C < 9,
+ * null pointers (out may be NULL in the device call), an unknown mode and a mask
+ * missing for the mode are reported (GGS_EINVAL) before any device is touched;
+ * a candidate whose strip partials (48 B per splat and 16 x 32 pixel strip)
+ * exceed the 40 MiB workspace budget is refused with GGS_ENOMEM.  The host call
+ * synchronises every stream it queued work on before returning, errors included. */
+int ggs_fitness_grad(const float* genomes_axes, int64_t B, int32_t N, int32_t C, const float* target_hw3,
+                     const float* mask_hw, int32_t mode, float boost_beta, int32_t H, int32_t W,
+                     float k_sigma, float* out_B, float* grad_BN9);
+int ggs_fitness_grad_device(int32_t device, void* stream, const float* d_genomes_axes, int64_t B, int32_t N,
+                            int32_t C, const float* d_target_hw3, const float* d_mask_hw, int32_t mode,
+                            float boost_beta, int32_t H, int32_t W, float k_sigma,
+                            float* d_out_B, float* d_grad_BN9);
+
+/* ---- Adam refiner --------------------------------------------------------------
+ * B candidates [B,N,9] refined side by side on the session's own stream.  Step t
+ * (from 1) evaluates fitness and gradient g of the state x_t, makes x_t the
+ * candidate's best so far iff fit + 1e-10 < best (float64), and updates in
+ * float32, every operation rounded once in this order (division and sqrt
+ * correctly rounded):
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) (g g)
+ *   x = x - (lr[c] (m / c1)) / (sqrt(v / c2) + eps),  c1 = float(1 - beta1^t), c2 likewise
+ * (the powers in float64), then clamp_genome's rule of column c (utils.py:35-45;
+ * an angle already in [-pi, pi) keeps its bits).  ggs/refine.py adam_step is the
+ * numpy statement a run is held to bit for bit.  From cfg: n_splats, H, W, k_sigma,
+ * the scale bounds, fitness_mode and boost_beta; the rest is ignored.  Argument
+ * errors as ggs_fitness_grad, plus lr < 0 or not finite, beta outside [0, 1) and
+ * eps <= 0 (GGS_EINVAL, before any device is touched). */
+typedef struct ggs_refine_params {
+    float lr[9];          /* per gene column: x, y, log a, log b, theta, r, g, b, alpha */
+    float beta1, beta2, eps;
+} ggs_refine_params;
+int ggs_refine_create(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p,
+                      const float* target_hw3, const float* mask_hw, const float* genomes_BN9, int32_t B,
+                      void** handle);
+int ggs_refine_run(void* handle, int32_t n_steps);      /* enqueues; no host synchronisation */
+/* Evaluates the current state (so fits belongs to genomes, and may become the best
+ * so far) and synchronises; any output may be NULL.  genomes, best, last_grad
+ * [B,N,9]; fits, best_fits [B].  last_grad: the gradient of the last step run. */
+int ggs_refine_read(void* handle, float* genomes, float* fits, float* best, float* best_fits, float* last_grad);
+void ggs_refine_destroy(void* handle);
+
 /* ---- multi-GPU fitness gather -------------------------------
  * One process per GPU; candidates are sharded in contiguous blocks and the only
  * exchange is an all-gather of each rank's fitness scalars over RCCL (xGMI).
