@@ -178,6 +178,7 @@ struct DevCtx {
     std::vector<std::unique_ptr<Workspace>> ws;
     // host-API staging
     DevBuf gen, out, target, mask, ggrad;   // ggrad: ggs_fitness_grad's [B,N,9]
+    DevBuf set_plan, set_wpart;            // ggs_fitness_grad_targets' own plan set
     DevBuf prep_in, prep_tgt, prep_mask;   // ggs_targets_prepare / ggs_quantiles staging
     PinBuf h_out;                  // the fitness scalars (render and genomes go straight to / from the caller)
     uint64_t target_key = 0, mask_key = 0;
@@ -546,13 +547,40 @@ int check_grad_dims(int64_t B, int32_t N, int32_t C, int32_t H, int32_t W, int32
     return GGS_OK;
 }
 
+// The gradient launches of a batch whose fitness has just run: prep's stage outputs,
+// then the strip / finish pair per chunk of candidates.  group == 0: one target and
+// mask, wblocks its plan's weight block; group > 0: candidate b against image
+// b / group of targets [K][H][W][3] / masks [K][H][W], wblocks the set's blocks.
+int run_grad_chunks(Workspace* w, hipStream_t st, const float* d_gen, int64_t B, int N, int C, const float* d_targets,
+                    const float* d_masks, int mode, float beta, int H, int W, float k, const float* wblocks,
+                    int group, float* d_grad) {
+    const size_t per = grad_partial_bytes(N, H, W);     // within the budget: check_grad_dims
+    const int64_t S = B * N;
+    const int chunk = (int)std::min<int64_t>(B, (int64_t)(kGradChunkBytes / per));
+    int rc;
+    if ((rc = ensure(w->gf9, sizeof(float) * 9 * (size_t)S, st))) return rc;
+    if ((rc = ensure(w->gi4, sizeof(int) * 4 * (size_t)S, st))) return rc;
+    if ((rc = ensure(w->gpart, per * (size_t)chunk, st))) return rc;
+    GGS_HIP(launch_prep(st, true, d_gen, S, C, H, W, k, nullptr, nullptr, (float*)w->gf9.p, (int*)w->gi4.p, nullptr));
+    const int64_t wstride = (int64_t)(plan_wsum_bytes(H, W) / sizeof(float));
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = (int)std::min<int64_t>(chunk, B - b0);
+        if (group > 0)      // a chunk may begin inside a group: the kernel takes b / group of the absolute b
+            GGS_HIP(launch_grad_set(st, d_gen, C, (const float*)w->gf9.p, (const int*)w->gi4.p, B, b0, nb, N, H, W,
+                                    d_targets, d_masks, mode, beta, wblocks, wstride, group, w->gpart.p, d_grad));
+        else
+            GGS_HIP(launch_grad(st, d_gen, C, (const float*)w->gf9.p, (const int*)w->gi4.p, B, b0, nb, N, H, W,
+                                d_targets, d_masks, mode, beta, wblocks, w->gpart.p, d_grad));
+    }
+    return GGS_OK;
+}
+
 // Fitness (the existing prep -> raster -> finalize path, so ggs_fitness_device's
 // bits) and its gradient [B][N][9].  d_out may be null.
 int run_fitness_grad(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C, const float* d_target,
                      const float* d_mask, int mode, float beta, int H, int W, float k, float* d_out, float* d_grad,
                      uint64_t plan_key = 0) {
     Workspace* w = workspace_for(c, st);
-    const size_t per = grad_partial_bytes(N, H, W);     // within the budget: check_grad_dims
     int rc;
     if (!d_out) {
         if ((rc = ensure(w->gout, sizeof(float) * (size_t)B, st))) return rc;
@@ -560,16 +588,36 @@ int run_fitness_grad(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, i
     }
     // first: it leaves the plan's weight block (the mode's Sum w) in the workspace
     if ((rc = run_fitness(c, st, d_gen, B, N, C, d_target, d_mask, mode, beta, H, W, k, d_out, plan_key))) return rc;
-    const int64_t S = B * N;
-    const int chunk = (int)std::min<int64_t>(B, (int64_t)(kGradChunkBytes / per));
-    if ((rc = ensure(w->gf9, sizeof(float) * 9 * (size_t)S, st))) return rc;
-    if ((rc = ensure(w->gi4, sizeof(int) * 4 * (size_t)S, st))) return rc;
-    if ((rc = ensure(w->gpart, per * (size_t)chunk, st))) return rc;
-    GGS_HIP(launch_prep(st, true, d_gen, S, C, H, W, k, nullptr, nullptr, (float*)w->gf9.p, (int*)w->gi4.p, nullptr));
-    for (int64_t b0 = 0; b0 < B; b0 += chunk)
-        GGS_HIP(launch_grad(st, d_gen, C, (const float*)w->gf9.p, (const int*)w->gi4.p, B, b0,
-                            (int)std::min<int64_t>(chunk, B - b0), N, H, W, d_target, d_mask, mode, beta,
-                            (const float*)w->wpartials.p, w->gpart.p, d_grad));
+    return run_grad_chunks(w, st, d_gen, B, N, C, d_target, d_mask, mode, beta, H, W, k, (const float*)w->wpartials.p,
+                           0, d_grad);
+}
+
+// The same against ready plans: group == 0 one plan (ggs_fitness_device_planned's
+// bits), group > 0 a plan set (ggs_fitness_device_planset's).  d_targets / d_masks:
+// the raw arrays the plans were made from.
+int run_fitness_grad_planned(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C,
+                             const float4* plan, const float* wblocks, const float* d_targets, const float* d_masks,
+                             int mode, float beta, int H, int W, int group, float k, float* d_out, float* d_grad) {
+    Workspace* w = workspace_for(c, st);
+    int rc;
+    if (!d_out) {
+        if ((rc = ensure(w->gout, sizeof(float) * (size_t)B, st))) return rc;
+        d_out = (float*)w->gout.p;
+    }
+    if ((rc = run_fitness_planned(c, st, d_gen, B, N, C, plan, wblocks, mode, H, W, k, d_out, group))) return rc;
+    return run_grad_chunks(w, st, d_gen, B, N, C, d_targets, d_masks, mode, beta, H, W, k, wblocks, group, d_grad);
+}
+
+// ggs_fitness_device_planset's rules on top of check_grad_dims (K: the set's plans)
+int check_grad_set(int64_t B, int32_t N, int32_t C, int32_t H, int32_t W, int32_t mode, const void* masks, int32_t K,
+                   int32_t group) {
+    if (group < 1) return fail(GGS_EINVAL, "group=%d must be >= 1", group);
+    if (K < 1) return fail(GGS_EINVAL, "K=%d images: must be >= 1", K);
+    int rc = check_grad_dims(B, N, C, H, W, mode, masks);
+    if (rc) return rc;
+    if (B % group != 0) return fail(GGS_EINVAL, "B=%lld is not a multiple of group=%d", (long long)B, group);
+    if (B / group > K)
+        return fail(GGS_EINVAL, "B / group = %lld images wanted, the set holds %d", (long long)(B / group), K);
     return GGS_OK;
 }
 
@@ -668,7 +716,8 @@ void ggs_shutdown(void) {
                               &w->swords, &w->smasks, &w->gf9, &w->gi4, &w->gpart, &w->gout})
                 if (b->p) (void)hipFree(b->p);
         }
-        for (DevBuf* b : {&c->gen, &c->out, &c->target, &c->mask, &c->ggrad, &c->prep_in, &c->prep_tgt, &c->prep_mask})
+        for (DevBuf* b : {&c->gen, &c->out, &c->target, &c->mask, &c->ggrad, &c->set_plan, &c->set_wpart, &c->prep_in,
+                          &c->prep_tgt, &c->prep_mask})
             if (b->p) (void)hipFree(b->p);
         for (PinBuf* b : {&c->h_out})
             if (b->p) (void)hipHostFree(b->p);
@@ -723,6 +772,7 @@ struct TargetPlan {
 struct PlanSet {
     DevCtx* c = nullptr;
     int H = 0, W = 0, mode = 0, K = 0;
+    float beta = 0.0f;              // the gradient's strip kernel needs it in BOOST mode
     DevBuf plan, wpartials;
 };
 }  // namespace
@@ -808,6 +858,7 @@ int ggs_planset_create(int32_t device, void* stream, const float* d_targets_khw3
     p->W = W;
     p->mode = mode;
     p->K = K;
+    p->beta = boost_beta;
     const hipStream_t st = (hipStream_t)stream;
     auto bail = [&](int code) {
         if (p->plan.p) (void)hipFree(p->plan.p);
@@ -839,6 +890,21 @@ int ggs_fitness_device_planset(void* planset, void* stream, const float* d_genom
     DeviceGuard dg(p->c->dev);
     return run_fitness_planned(p->c, (hipStream_t)stream, d_genomes_axes, B, N, C, (const float4*)p->plan.p,
                                (const float*)p->wpartials.p, p->mode, p->H, p->W, k_sigma, d_out_B, group);
+}
+
+int ggs_fitness_grad_device_planset(void* planset, void* stream, const float* d_genomes_axes, int64_t B, int32_t N,
+                                    int32_t C, int32_t group, const float* d_targets_khw3, const float* d_masks_khw,
+                                    float k_sigma, float* d_out_B, float* d_grad_BN9) {
+    if (!planset) return fail(GGS_EINVAL, "null plan set");
+    PlanSet* p = (PlanSet*)planset;
+    int rc = check_grad_set(B, N, C, p->H, p->W, p->mode, d_masks_khw, p->K, group);
+    if (rc) return rc;
+    if (!d_genomes_axes || !d_targets_khw3 || !d_grad_BN9) return fail(GGS_EINVAL, "null genomes/targets/grad");
+    std::lock_guard<std::mutex> lk(p->c->mu);
+    DeviceGuard dg(p->c->dev);
+    return run_fitness_grad_planned(p->c, (hipStream_t)stream, d_genomes_axes, B, N, C, (const float4*)p->plan.p,
+                                    (const float*)p->wpartials.p, d_targets_khw3, d_masks_khw, p->mode, p->beta,
+                                    p->H, p->W, group, k_sigma, d_out_B, d_grad_BN9);
 }
 
 void ggs_planset_destroy(void* planset) {
@@ -1189,6 +1255,47 @@ int ggs_fitness_grad(const float* genomes_axes, int64_t B, int32_t N, int32_t C,
     GGS_HIP(hipMemcpyAsync(out_B, c->out.p, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st));
     GGS_HIP(hipMemcpyAsync(grad_BN9, c->ggrad.p, dbytes, hipMemcpyDeviceToHost, st));
     if (inject_fail_after(1)) return fail(GGS_EHIP, "injected failure after device 1's work (test hook)");
+    return drain.drain();
+}
+
+int ggs_fitness_grad_targets(const float* genomes_axes, int64_t B, int32_t N, int32_t C, const float* targets_khw3,
+                             const float* masks_khw, int32_t K, int32_t group, int32_t mode, float boost_beta,
+                             int32_t H, int32_t W, float k_sigma, float* out_B, float* grad_BN9) {
+    int rc = check_grad_set(B, N, C, H, W, mode, masks_khw, K, group);
+    if (rc) return rc;
+    if (!genomes_axes || !targets_khw3 || !out_B || !grad_BN9) return fail(GGS_EINVAL, "null pointer");
+    if ((rc = check_dims(K, 1, 9, H, W))) return rc;      // the set's strips are numbered through in 32 bits
+    std::vector<DevCtx*> cs;
+    if ((rc = active_ctxs(1, &cs))) return rc;
+    DevCtx* c = cs[0];
+    const size_t tbytes = sizeof(float) * 3 * (size_t)H * W * (size_t)K, mbytes = sizeof(float) * (size_t)H * W * (size_t)K;
+    const size_t gbytes = sizeof(float) * (size_t)N * C * (size_t)B, dbytes = sizeof(float) * 9 * (size_t)N * (size_t)B;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    hipStream_t st = c->stream;
+    StreamDrain drain;                  // after the context lock: drained on every return
+    if ((rc = ensure(c->out, sizeof(float) * (size_t)B, st)) || (rc = ensure(c->ggrad, dbytes, st)) ||
+        (rc = ensure(c->target, tbytes, st)) || (masks_khw && (rc = ensure(c->mask, mbytes, st))) ||
+        (rc = ensure(c->gen, gbytes, st)) || (rc = ensure(c->set_plan, (size_t)K * plan_bytes(H, W), st)) ||
+        (rc = ensure(c->set_wpart, (size_t)K * plan_wsum_bytes(H, W), st)))
+        return rc;
+    GGS_HIP(hipStreamSynchronize(st));  // the previous call's work is done with the staging
+    drain.add(c->dev, st);
+    // the staging no longer holds what the single-target calls' content keys describe
+    c->target_key = c->mask_key = 0;
+    c->target_bytes = c->mask_bytes = 0;
+    GGS_HIP(hipMemcpyAsync(c->target.p, targets_khw3, tbytes, hipMemcpyHostToDevice, st));
+    if (masks_khw) GGS_HIP(hipMemcpyAsync(c->mask.p, masks_khw, mbytes, hipMemcpyHostToDevice, st));
+    GGS_HIP(hipMemcpyAsync(c->gen.p, genomes_axes, gbytes, hipMemcpyHostToDevice, st));
+    const float* d_masks = masks_khw ? (const float*)c->mask.p : nullptr;
+    GGS_HIP(launch_plan_set(st, (const float*)c->target.p, d_masks, mode, boost_beta, H, W, K,
+                            (float4*)c->set_plan.p, (float*)c->set_wpart.p));
+    if ((rc = run_fitness_grad_planned(c, st, (const float*)c->gen.p, B, N, C, (const float4*)c->set_plan.p,
+                                       (const float*)c->set_wpart.p, (const float*)c->target.p, d_masks, mode,
+                                       boost_beta, H, W, group, k_sigma, (float*)c->out.p, (float*)c->ggrad.p)))
+        return rc;
+    GGS_HIP(hipMemcpyAsync(out_B, c->out.p, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st));
+    GGS_HIP(hipMemcpyAsync(grad_BN9, c->ggrad.p, dbytes, hipMemcpyDeviceToHost, st));
     return drain.drain();
 }
 
@@ -1804,6 +1911,68 @@ void ggs_ga_destroy(void* handle) {
 
 }  // extern "C"
 
+// ---- Adam refiner: what the refine sessions and the island group's polish share ----
+namespace ggs {
+namespace {
+int refine_check_params(const ggs_refine_params* p) {
+    if (!p) return fail(GGS_EINVAL, "null ggs_refine_params");
+    for (int c = 0; c < 9; ++c)
+        if (!std::isfinite(p->lr[c]) || p->lr[c] < 0.0f) return fail(GGS_EINVAL, "lr[%d]=%g must be finite and >= 0", c, p->lr[c]);
+    if (!(p->beta1 >= 0.0f && p->beta1 < 1.0f)) return fail(GGS_EINVAL, "beta1=%g must be in [0, 1)", p->beta1);
+    if (!(p->beta2 >= 0.0f && p->beta2 < 1.0f)) return fail(GGS_EINVAL, "beta2=%g must be in [0, 1)", p->beta2);
+    if (!(p->eps > 0.0f) || !std::isfinite(p->eps)) return fail(GGS_EINVAL, "eps=%g must be > 0", p->eps);
+    return GGS_OK;
+}
+
+// step t's constants (t from 1); cfg: the scale bounds, filled (ga_fill_log_bounds)
+RefineStepDev refine_step_dev(const ggs_refine_params& prm, const ggs_ga_config& cfg, int64_t t) {
+    RefineStepDev p;
+    for (int c = 0; c < 9; ++c) p.lr[c] = prm.lr[c];
+    p.beta1 = prm.beta1;
+    p.beta2 = prm.beta2;
+    p.eps = prm.eps;
+    p.c1 = (float)(1.0 - pow((double)prm.beta1, (double)t));
+    p.c2 = (float)(1.0 - pow((double)prm.beta2, (double)t));
+    p.log_lo = cfg.scale_log_lo;
+    p.log_hi = cfg.scale_log_hi;
+    return p;
+}
+
+// A session's stream is about to be destroyed: the context's pipeline workspace of
+// that stream goes with it (a later stream may get the same handle).
+void release_workspace(DevCtx* c, hipStream_t st) {
+    for (auto it = c->ws.begin(); it != c->ws.end(); ++it)
+        if ((*it)->stream == st) {
+            Workspace* w = it->get();
+            for (DevBuf* b : {&w->recs, &w->bnds, &w->partials, &w->wpartials, &w->order, &w->plan, &w->fctr,
+                              &w->maskws, &w->swords, &w->smasks, &w->gf9, &w->gi4, &w->gpart, &w->gout})
+                if (b->p) (void)hipFree(b->p);
+            c->ws.erase(it);
+            return;
+        }
+}
+
+// The pipeline buffers a gradient call over B candidates takes from the stream's
+// workspace, made now so that no later call allocates.
+int reserve_grad_workspace(DevCtx* c, hipStream_t st, int64_t B, int N, int H, int W) {
+    Workspace* w = workspace_for(c, st);
+    int nTX;
+    const int nTiles = raster_tiles(H, W, &nTX);
+    const size_t per = grad_partial_bytes(N, H, W), S = (size_t)B * N;
+    const int64_t chunk = std::min<int64_t>(B, (int64_t)(kGradChunkBytes / per));
+    int rc;
+    StripWords sw;
+    if ((rc = ensure(w->recs, sizeof(SplatRec) * S, st)) || (rc = ensure(w->bnds, sizeof(int4) * S, st)) ||
+        (rc = ensure(w->partials, sizeof(float) * 4 * (size_t)(B * nTiles), st)) ||
+        (rc = ensure_tile_order(w, H, W, st)) || (rc = ensure_strip_words(w, B, N, H, W, st, &sw)) ||
+        (rc = ensure(w->gf9, sizeof(float) * 9 * S, st)) || (rc = ensure(w->gi4, sizeof(int) * 4 * S, st)) ||
+        (rc = ensure(w->gpart, per * (size_t)chunk, st)))
+        return rc;
+    return GGS_OK;
+}
+}  // namespace
+}  // namespace ggs
+
 // ---- island groups (ggs_ga_islands_*) -------------------------------------------
 namespace ggs {
 namespace {
@@ -1832,15 +2001,24 @@ struct GaIslands {
     // their genomes staged compactly; mig_fits [K][m])
     bool multi = false;
     DevBuf mig_gen, mig_fits;
+    // memetic generations (ggs_ga_islands_set_polish; every or n_steps 0: off): island
+    // k's n_rows best-ranked rows are refine candidates k * n_rows + j
+    ggs_ga_polish polish{};
+    DevBuf px, pm, pv, pgrad, pbest_x, pbest_fit, pfits, prows;
 };
 
 void gi_free(GaIslands* s) {
     for (DevBuf* b : {&s->pop[0], &s->pop[1], &s->fits[0], &s->fits[1], &s->off[0], &s->off[1], &s->elite[0],
                       &s->elite[1], &s->off_fits, &s->src, &s->target, &s->mask, &s->best_ind, &s->best_fit,
                       &s->best_src, &s->best_upd, &s->curves, &s->seeds, &s->mig, &s->recs, &s->bnds,
-                      &s->partials, &s->plan, &s->wpart, &s->order, &s->fctr, &s->mig_gen, &s->mig_fits})
+                      &s->partials, &s->plan, &s->wpart, &s->order, &s->fctr, &s->mig_gen, &s->mig_fits, &s->px,
+                      &s->pm, &s->pv, &s->pgrad, &s->pbest_x, &s->pbest_fit, &s->pfits, &s->prows})
         if (b->p) (void)hipFree(b->p);
-    if (s->st) (void)hipStreamDestroy(s->st);
+    if (s->st) {
+        // the initial evaluation and the polish run through the stream's workspace
+        release_workspace(s->c, s->st);
+        (void)hipStreamDestroy(s->st);
+    }
 }
 
 GaBestDev gi_best(GaIslands* s) {
@@ -1878,7 +2056,50 @@ bool gi_fused() {
     return !off;
 }
 
-// ga_flush for the group, then the pending generation's migration if it is due.
+bool gi_polishes(const GaIslands* s, int gen) {
+    return s->polish.every > 0 && s->polish.n_steps > 0 && gen % s->polish.every == 0;
+}
+
+// One polish of every island, all on the session's stream: the ranked rows staged
+// as K * n_rows refine candidates (zero moments, t from 1), n_steps steps as
+// ggs_refine_run takes them and ggs_refine_read's closing evaluation, each one
+// chain of launches for all candidates against their island's image, then the
+// install (strictly lower only), the elite lists and the best so far.
+int gi_polish(GaIslands* s) {
+    const ggs_ga_config& c = s->cfg;
+    const int R = s->polish.n_rows, B = s->K * R, N = s->N, cur = s->cur;
+    const size_t pb = sizeof(float) * 9 * (size_t)B * N;
+    const float* d_mask = s->mask.p ? (const float*)s->mask.p : nullptr;
+    const int group = s->multi ? R : 0;     // a shared target: the one plan, ggs_refine_create's path
+    int rc;
+    GGS_HIP(launch_polish_stage(s->st, s->K, (const float*)s->pop[cur].p, (const float*)s->fits[cur].p, s->P, N, R,
+                                (int*)s->prows.p, (float*)s->px.p, (float*)s->pbest_x.p, (double*)s->pbest_fit.p));
+    GGS_HIP(hipMemsetAsync(s->pm.p, 0, pb, s->st));
+    GGS_HIP(hipMemsetAsync(s->pv.p, 0, pb, s->st));
+    for (int t = 1; t <= s->polish.n_steps; ++t) {
+        if ((rc = run_fitness_grad_planned(s->c, s->st, (const float*)s->px.p, B, N, 9, (const float4*)s->plan.p,
+                                           (const float*)s->wpart.p, (const float*)s->target.p, d_mask,
+                                           c.fitness_mode, c.boost_beta, c.H, c.W, group, c.k_sigma,
+                                           (float*)s->pfits.p, (float*)s->pgrad.p)))
+            return rc;
+        GGS_HIP(launch_refine_best(s->st, (const float*)s->px.p, (const float*)s->pfits.p, B, N,
+                                   (double*)s->pbest_fit.p, (float*)s->pbest_x.p));
+        GGS_HIP(launch_refine_adam(s->st, (float*)s->px.p, (float*)s->pm.p, (float*)s->pv.p, (const float*)s->pgrad.p,
+                                   B, N, refine_step_dev(s->polish.adam, c, t)));
+    }
+    if ((rc = run_fitness_planned(s->c, s->st, (const float*)s->px.p, B, N, 9, (const float4*)s->plan.p,
+                                  (const float*)s->wpart.p, c.fitness_mode, c.H, c.W, c.k_sigma, (float*)s->pfits.p,
+                                  group)))
+        return rc;
+    GGS_HIP(launch_refine_best(s->st, (const float*)s->px.p, (const float*)s->pfits.p, B, N, (double*)s->pbest_fit.p,
+                               (float*)s->pbest_x.p));
+    GGS_HIP(launch_polish_install(s->st, s->K, (float*)s->pop[cur].p, (float*)s->fits[cur].p, s->P, N, R, c.elite_k,
+                                  (const int*)s->prows.p, (const float*)s->pbest_x.p, (const double*)s->pbest_fit.p,
+                                  (int*)s->elite[cur].p, (double*)s->best_fit.p, (float*)s->best_ind.p));
+    return GGS_OK;
+}
+
+// ga_flush for the group, then the pending generation's migration and polish if they are due.
 int gi_flush(GaIslands* s) {
     if (!s->pending) return GGS_OK;
     const int nxt = 1 - s->cur;
@@ -1920,6 +2141,7 @@ int gi_flush(GaIslands* s) {
         GGS_HIP(launch_ga_migrate_install(s->st, s->K, (float*)s->fits[nxt].p, s->P, m, c.elite_k,
                                           (const int*)s->mig.p, (const float*)s->mig_fits.p, (int*)s->elite[nxt].p));
     }
+    if (gi_polishes(s, s->pending_gen) && (rc = gi_polish(s))) return rc;
     return GGS_OK;
 }
 
@@ -1929,9 +2151,9 @@ int gi_generation(GaIslands* s, int gen, int total) {
     const GaParamsDev prm = ga_params(c, gen, total);
     const int onew = 1 - s->ocur;
     int rc;
-    // a generation whose survivors are followed by a migration is closed unfused
-    // (flush, migrate); the plain variation launch then breeds from pop / fits
-    if (s->pending && gi_fused() && !gi_migrates(s, s->pending_gen)) {
+    // a generation whose survivors are followed by a migration or a polish is closed
+    // unfused (flush, migrate, polish); the plain variation launch then breeds from pop / fits
+    if (s->pending && gi_fused() && !gi_migrates(s, s->pending_gen) && !gi_polishes(s, s->pending_gen)) {
         const int nxt = 1 - s->cur;
         double* row;
         if ((rc = gi_curves_row(s, &row))) return rc;
@@ -2110,6 +2332,44 @@ int ggs_ga_islands_run(void* handle, int32_t first_gen, int32_t n_gens, int32_t 
         const int rc = gi_generation(s, first_gen + g, total_gens);
         if (rc) return rc;
     }
+    return GGS_OK;
+}
+
+int ggs_ga_islands_set_polish(void* handle, const ggs_ga_polish* polish) {
+    if (!handle) return fail(GGS_EINVAL, "null handle");
+    GaIslands* s = (GaIslands*)handle;
+    std::lock_guard<std::mutex> lk(s->c->mu);
+    if (!polish) {
+        DeviceGuard dg(s->c->dev);
+        const int rc = gi_flush(s);     // a generation already run is closed under the setting it ran with
+        if (rc) return rc;
+        s->polish = ggs_ga_polish{};
+        return GGS_OK;
+    }
+    const ggs_ga_polish& q = *polish;
+    const int Emax = std::max(1, s->cfg.elite_k);
+    if (q.every < 0 || q.n_steps < 0) return fail(GGS_EINVAL, "every=%d and n_steps=%d must be >= 0", q.every, q.n_steps);
+    if (q.n_rows < 1 || q.n_rows > Emax)
+        return fail(GGS_EINVAL, "n_rows must be in [1, max(1, elite_k) = %d], got %d", Emax, q.n_rows);
+    int rc = refine_check_params(&q.adam);
+    if (rc) return rc;
+    if (s->P > polish_max_population())
+        return fail(GGS_EINVAL, "an island's pop_size must be <= %d, got %d", polish_max_population(), s->P);
+    const ggs_ga_config& c = s->cfg;
+    const int64_t B = (int64_t)s->K * q.n_rows;
+    // the candidates' batch limits and the partial budget (GGS_ENOMEM)
+    if ((rc = check_grad_dims(B, s->N, 9, c.H, c.W, c.fitness_mode, s->mask.p))) return rc;
+    DeviceGuard dg(s->c->dev);
+    const size_t pb = sizeof(float) * 9 * (size_t)B * s->N;
+    if ((rc = ensure(s->px, pb, s->st)) || (rc = ensure(s->pm, pb, s->st)) || (rc = ensure(s->pv, pb, s->st)) ||
+        (rc = ensure(s->pgrad, pb, s->st)) || (rc = ensure(s->pbest_x, pb, s->st)) ||
+        (rc = ensure(s->pbest_fit, sizeof(double) * (size_t)B, s->st)) ||
+        (rc = ensure(s->pfits, sizeof(float) * (size_t)B, s->st)) ||
+        (rc = ensure(s->prows, sizeof(int) * (size_t)B, s->st)) ||
+        (rc = reserve_grad_workspace(s->c, s->st, B, s->N, c.H, c.W)))
+        return rc;              // buffers only grew: the session's settings are as they were
+    if ((rc = gi_flush(s))) return rc;  // a generation already run is closed under the setting it ran with
+    s->polish = q;
     return GGS_OK;
 }
 
@@ -3206,42 +3466,38 @@ struct RefineSession {
     int64_t t = 0;                 // Adam steps taken
     uint64_t plan_key = 0;         // the session's target never changes
     DevBuf x, m, v, grad, fits, best_x, best_fit, target, mask;
+    // ggs_refine_create_targets: target [K][H][W][3], mask [K][H][W], plan / wpart a plan
+    // set of K made at create; candidate b against image b / group (0: the one target)
+    int K = 1, group = 0;
+    DevBuf plan, wpart;
 };
 
 std::atomic<uint64_t> g_refine_serial{1};
 
 void refine_free(RefineSession* s) {
-    for (DevBuf* b : {&s->x, &s->m, &s->v, &s->grad, &s->fits, &s->best_x, &s->best_fit, &s->target, &s->mask})
+    for (DevBuf* b : {&s->x, &s->m, &s->v, &s->grad, &s->fits, &s->best_x, &s->best_fit, &s->target, &s->mask,
+                      &s->plan, &s->wpart})
         if (b->p) (void)hipFree(b->p);
     if (s->st) {
-        // the stream's workspace goes with it (a later stream may get the same handle)
-        for (auto it = s->c->ws.begin(); it != s->c->ws.end(); ++it)
-            if ((*it)->stream == s->st) {
-                Workspace* w = it->get();
-                for (DevBuf* b : {&w->recs, &w->bnds, &w->partials, &w->wpartials, &w->order, &w->plan, &w->fctr,
-                                  &w->maskws, &w->swords, &w->smasks, &w->gf9, &w->gi4, &w->gpart, &w->gout})
-                    if (b->p) (void)hipFree(b->p);
-                s->c->ws.erase(it);
-                break;
-            }
+        release_workspace(s->c, s->st);
         (void)hipStreamDestroy(s->st);
     }
-}
-
-int refine_check_params(const ggs_refine_params* p) {
-    if (!p) return fail(GGS_EINVAL, "null ggs_refine_params");
-    for (int c = 0; c < 9; ++c)
-        if (!std::isfinite(p->lr[c]) || p->lr[c] < 0.0f) return fail(GGS_EINVAL, "lr[%d]=%g must be finite and >= 0", c, p->lr[c]);
-    if (!(p->beta1 >= 0.0f && p->beta1 < 1.0f)) return fail(GGS_EINVAL, "beta1=%g must be in [0, 1)", p->beta1);
-    if (!(p->beta2 >= 0.0f && p->beta2 < 1.0f)) return fail(GGS_EINVAL, "beta2=%g must be in [0, 1)", p->beta2);
-    if (!(p->eps > 0.0f) || !std::isfinite(p->eps)) return fail(GGS_EINVAL, "eps=%g must be > 0", p->eps);
-    return GGS_OK;
 }
 
 // fitness (and, with grad, the gradient) of the current state into s->fits
 int refine_eval(RefineSession* s, bool grad) {
     const ggs_ga_config& c = s->cfg;
     const float* d_mask = s->mask.p ? (const float*)s->mask.p : nullptr;
+    if (s->group > 0) {
+        if (grad)
+            return run_fitness_grad_planned(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, (const float4*)s->plan.p,
+                                            (const float*)s->wpart.p, (const float*)s->target.p, d_mask,
+                                            c.fitness_mode, c.boost_beta, c.H, c.W, s->group, c.k_sigma,
+                                            (float*)s->fits.p, (float*)s->grad.p);
+        return run_fitness_planned(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, (const float4*)s->plan.p,
+                                   (const float*)s->wpart.p, c.fitness_mode, c.H, c.W, c.k_sigma, (float*)s->fits.p,
+                                   s->group);
+    }
     if (grad)
         return run_fitness_grad(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, (const float*)s->target.p, d_mask,
                                 c.fitness_mode, c.boost_beta, c.H, c.W, c.k_sigma, (float*)s->fits.p,
@@ -3250,17 +3506,16 @@ int refine_eval(RefineSession* s, bool grad) {
                        c.fitness_mode, c.boost_beta, c.H, c.W, c.k_sigma, (float*)s->fits.p, s->plan_key);
 }
 
-}  // namespace
-}  // namespace ggs
-
-extern "C" {
-
-int ggs_refine_create(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p, const float* target_hw3,
-                      const float* mask_hw, const float* genomes_BN9, int32_t B, void** handle) {
-    if (!cfg || !p || !target_hw3 || !genomes_BN9 || !handle) return fail(GGS_EINVAL, "null argument");
+// ggs_refine_create (group 0: one target and mask) and ggs_refine_create_targets
+// (group >= 1: targets [K][H][W][3], masks [K][H][W], one plan set)
+int refine_create(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p, const float* target,
+                  const float* mask, int32_t K, const float* genomes_BN9, int32_t B, int32_t group, void** handle) {
+    if (!cfg || !p || !target || !genomes_BN9 || !handle) return fail(GGS_EINVAL, "null argument");
     const ggs_ga_config& c = *cfg;
-    int rc = check_grad_dims(B, c.n_splats, 9, c.H, c.W, c.fitness_mode, mask_hw);
+    int rc = group == 0 ? check_grad_dims(B, c.n_splats, 9, c.H, c.W, c.fitness_mode, mask)
+                        : check_grad_set(B, c.n_splats, 9, c.H, c.W, c.fitness_mode, mask, K, group);
     if (rc) return rc;
+    if (group > 0 && (rc = check_dims(K, 1, 9, c.H, c.W))) return rc;
     if ((rc = refine_check_params(p))) return rc;
     DevCtx* ctx = nullptr;
     if ((rc = get_ctx(device, &ctx))) return rc;
@@ -3271,8 +3526,10 @@ int ggs_refine_create(int32_t device, const ggs_ga_config* cfg, const ggs_refine
     ga_fill_log_bounds(&s->cfg);
     s->B = B;
     s->N = c.n_splats;
+    s->K = K;
+    s->group = group;
     s->plan_key = (1ull << 63) | g_refine_serial.fetch_add(1);     // host_plan_key never sets bit 63
-    const size_t pb = sizeof(float) * 9 * (size_t)B * s->N, hw = (size_t)c.H * c.W;
+    const size_t pb = sizeof(float) * 9 * (size_t)B * s->N, hw = (size_t)K * c.H * c.W;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard dg(ctx->dev);
     auto bail = [&](int code) { refine_free(s.get()); return code; };
@@ -3283,21 +3540,42 @@ int ggs_refine_create(int32_t device, const ggs_ga_config* cfg, const ggs_refine
         (rc = ensure(s->fits, sizeof(float) * (size_t)B, s->st)) ||
         (rc = ensure(s->best_fit, sizeof(double) * (size_t)B, s->st)) ||
         (rc = ensure(s->target, sizeof(float) * 3 * hw, s->st)) ||
-        (mask_hw && (rc = ensure(s->mask, sizeof(float) * hw, s->st))))
+        (mask && (rc = ensure(s->mask, sizeof(float) * hw, s->st))) ||
+        (group > 0 && ((rc = ensure(s->plan, (size_t)K * plan_bytes(c.H, c.W), s->st)) ||
+                       (rc = ensure(s->wpart, (size_t)K * plan_wsum_bytes(c.H, c.W), s->st)))))
         return bail(rc);
     std::vector<double> inf((size_t)B, (double)INFINITY);
-    if (hipMemcpyAsync(s->target.p, target_hw3, sizeof(float) * 3 * hw, hipMemcpyHostToDevice, s->st) ||
-        (mask_hw && hipMemcpyAsync(s->mask.p, mask_hw, sizeof(float) * hw, hipMemcpyHostToDevice, s->st)) ||
+    if (hipMemcpyAsync(s->target.p, target, sizeof(float) * 3 * hw, hipMemcpyHostToDevice, s->st) ||
+        (mask && hipMemcpyAsync(s->mask.p, mask, sizeof(float) * hw, hipMemcpyHostToDevice, s->st)) ||
         hipMemcpyAsync(s->x.p, genomes_BN9, pb, hipMemcpyHostToDevice, s->st) ||
         hipMemcpyAsync(s->best_x.p, genomes_BN9, pb, hipMemcpyHostToDevice, s->st) ||
         hipMemcpyAsync(s->best_fit.p, inf.data(), sizeof(double) * (size_t)B, hipMemcpyHostToDevice, s->st) ||
         hipMemsetAsync(s->m.p, 0, pb, s->st) || hipMemsetAsync(s->v.p, 0, pb, s->st) ||
         hipMemsetAsync(s->grad.p, 0, pb, s->st))
         return bail(fail(GGS_EHIP, "upload failed"));
+    if (group > 0 &&
+        launch_plan_set(s->st, (const float*)s->target.p, mask ? (const float*)s->mask.p : nullptr, c.fitness_mode,
+                        c.boost_beta, c.H, c.W, K, (float4*)s->plan.p, (float*)s->wpart.p) != hipSuccess)
+        return bail(fail(GGS_EHIP, "plan launch failed"));
     if (hipStreamSynchronize(s->st) != hipSuccess)     // the caller's arrays may be freed on return
         return bail(fail(GGS_EHIP, "upload failed"));
     *handle = s.release();
     return GGS_OK;
+}
+}  // namespace
+}  // namespace ggs
+extern "C" {
+
+int ggs_refine_create(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p, const float* target_hw3,
+                      const float* mask_hw, const float* genomes_BN9, int32_t B, void** handle) {
+    return ggs::refine_create(device, cfg, p, target_hw3, mask_hw, 1, genomes_BN9, B, 0, handle);
+}
+
+int ggs_refine_create_targets(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p,
+                              const float* targets_khw3, const float* masks_khw, int32_t K, const float* genomes_BN9,
+                              int32_t B, int32_t group, void** handle) {
+    if (group < 1) return fail(GGS_EINVAL, "group=%d must be >= 1", group);
+    return ggs::refine_create(device, cfg, p, targets_khw3, masks_khw, K, genomes_BN9, B, group, handle);
 }
 
 int ggs_refine_run(void* handle, int32_t n_steps) {
@@ -3311,15 +3589,7 @@ int ggs_refine_run(void* handle, int32_t n_steps) {
         GGS_HIP(launch_refine_best(s->st, (const float*)s->x.p, (const float*)s->fits.p, s->B, s->N,
                                    (double*)s->best_fit.p, (float*)s->best_x.p));
         s->t += 1;
-        RefineStepDev p;
-        for (int c = 0; c < 9; ++c) p.lr[c] = s->prm.lr[c];
-        p.beta1 = s->prm.beta1;
-        p.beta2 = s->prm.beta2;
-        p.eps = s->prm.eps;
-        p.c1 = (float)(1.0 - pow((double)s->prm.beta1, (double)s->t));
-        p.c2 = (float)(1.0 - pow((double)s->prm.beta2, (double)s->t));
-        p.log_lo = s->cfg.scale_log_lo;
-        p.log_hi = s->cfg.scale_log_hi;
+        const RefineStepDev p = refine_step_dev(s->prm, s->cfg, s->t);
         GGS_HIP(launch_refine_adam(s->st, (float*)s->x.p, (float*)s->m.p, (float*)s->v.p, (const float*)s->grad.p,
                                    s->B, s->N, p));
     }

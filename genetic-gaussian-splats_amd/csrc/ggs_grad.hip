@@ -1,6 +1,6 @@
 // Fitness gradients: d fitness / d genome for the nine axes-angle
-// genes of every splat, and the Adam refiner's elementwise kernels.
-//
+// genes of every splat, the Adam refiner's elementwise kernels and (§8d) the set
+// kernel grad_set_strip_kernel with the island polish's polish_stage / _install.
 //   grad_strip_kernel   one wave per (candidate, 16 x 32 pixel strip): the per-pixel
 //                       backward of the "over" blend, reduced over the strip to nine
 //                       sums per visited splat -> partials [b][strip][splat][12]
@@ -176,127 +176,28 @@ grad_strip_kernel(const float* __restrict__ f9, const int* __restrict__ i4, int6
     const int lane = (int)threadIdx.x;
     const int bl = (int)(blockIdx.x / (unsigned)nStrips);
     const int strip = (int)(blockIdx.x % (unsigned)nStrips);
-    const int sx = strip % nSX, sy = strip / nSX;
-    const int64_t base = (b0 + bl) * (int64_t)N;
-    const int X = sx * GS_W + (lane & 15);
-    const int Y0 = sy * GS_H + (lane >> 4);
-    const float xf = (float)X;
-    const int nC = (N + 63) / 64;
+#include "ggs_grad_strip.inc"
+}
 
-    // ---- sweep 1: the unclipped final colour ---------------------------------
-    float cr[GPL], cg[GPL], cb[GPL];
-#pragma unroll
-    for (int j = 0; j < GPL; ++j) cr[j] = cg[j] = cb[j] = 1.0f;     // fitness.py:15: white background
-    canvas_upto(f9, i4, S, base, N, N, lane, sx, sy, X, Y0, cr, cg, cb);
-
-    // ---- g = dL/dCf per channel (0 where the image clip is active), S = g . Cf ----
-    const double hw = (double)H * (double)W;
-    double D;
-    if (mode == GGS_FIT_NONE) D = 3.0 * hw;                          // fitness.py:18-19
-    else if (mode == GGS_FIT_WEIGHTED) D = *wsum + 1e-12;            // fitness.py:28-31
-    else D = 3.0 * hw * (*wsum / hw + 1e-12);                        // fitness.py:23-27
-    const float coef = (float)(2.0 / D);
-    float T[GPL], Sg[GPL], gr[GPL], gg[GPL], gb[GPL];
-#pragma unroll
-    for (int j = 0; j < GPL; ++j) {
-        const int y = Y0 + 4 * j;
-        float r = 0.0f, g = 0.0f, b = 0.0f;
-        if (X < W && y < H) {
-            const int64_t p = (int64_t)y * W + X;
-            float om = 1.0f;
-            if (mode == GGS_FIT_WEIGHTED) om = mask[p];
-            else if (mode == GGS_FIT_BOOST) om = 1.0f + beta * fminf(fmaxf(mask[p], 0.0f), 1.0f);
-            const float k = om * coef;
-            const float tr = target[3 * p + 0], tg = target[3 * p + 1], tb = target[3 * p + 2];
-            r = (cr[j] >= 0.0f && cr[j] <= 1.0f) ? (cr[j] - tr) * k : 0.0f;
-            g = (cg[j] >= 0.0f && cg[j] <= 1.0f) ? (cg[j] - tg) * k : 0.0f;
-            b = (cb[j] >= 0.0f && cb[j] <= 1.0f) ? (cb[j] - tb) * k : 0.0f;
-        }
-        gr[j] = r;
-        gg[j] = g;
-        gb[j] = b;
-        Sg[j] = (r * cr[j] + g * cg[j]) + b * cb[j];
-        T[j] = 1.0f;
-    }
-
-    // ---- sweep 2: front to back ------------------------------------------------
-    float4* const out = part + ((int64_t)bl * nStrips + strip) * (int64_t)N * 3;
-    for (int c = nC - 1; c >= 0; --c) {
-        uint64_t m = cull_chunk(i4, S, base, N, c, lane, sx, sy);
-        while (m) {
-            const int bit = 63 - __builtin_clzll(m);
-            m &= ~(1ull << bit);
-            const int i = c * 64 + bit;
-            const GSplat s = load_splat(f9, i4, S, base + i);
-            const bool in_x = X >= s.x0 && X <= s.x1;
-            const float qx = xf - s.cx;
-            const int yb = opaque(Y0);
-            // 1 - f >= 1 - a: only a nearly opaque splat can need the exact walk
-            bool exact = false;
-            if (s.a > 1.0f - ONE_MINUS_F_MIN) {
-                bool low = false;
-#pragma unroll
-                for (int j = 0; j < GPL; ++j) {
-                    const int y = yb + 4 * j;
-                    float qy;
-                    const float e = gauss(s, in_x, qx, (float)y, y, &qy);
-                    low = low || (e > 0.0f && 1.0f - e * s.a < ONE_MINUS_F_MIN);
-                }
-                exact = __builtin_amdgcn_ballot_w64(low) != 0ull;
-            }
-            // exact: u = g . canvas_{i-1}, linear in the canvas, so the walk carries one
-            // float per pixel: u <- (1 - f) u + f (g . c) from u = g . background
-            float u[GPL];
-            if (exact) {
-#pragma unroll
-                for (int j = 0; j < GPL; ++j) u[j] = (gr[j] + gg[j]) + opaque(gb[j]);
-                gdot_canvas_upto(f9, i4, S, base, N, i, lane, sx, sy, X, Y0, gr, gg, gb, u);
-            }
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f, a8 = 0.f;
-#pragma unroll
-            for (int j = 0; j < GPL; ++j) {
-                const int y = yb + 4 * j;
-                float qy;
-                const float e = gauss(s, in_x, qx, (float)y, y, &qy);
-                const float f = e * s.a;
-                const float gc = (gr[j] * s.r + gg[j] * s.g) + gb[j] * s.b;
-                const float w = T[j] * f;
-                const float wgc = w * gc;
-                const float rest = Sg[j] - wgc;          // T (1 - f) g . canvas_{i-1}
-                float back;                               // T g . canvas_{i-1}
-                if (exact) back = T[j] * u[j];
-                else back = rest * __builtin_amdgcn_rcpf(1.0f - f);
-                const float dLdf = T[j] * gc - back;
-                const float h = dLdf * f;
-                const float hx = h * qx, hy = h * qy;
-                a0 += hx;
-                a1 += hy;
-                a2 += hx * qx;
-                a3 += hx * qy;
-                a4 += hy * qy;
-                a5 += dLdf * e;
-                a6 += w * gr[j];
-                a7 += w * gg[j];
-                a8 += w * gb[j];
-                Sg[j] = rest;
-                T[j] = T[j] - w;
-            }
-            a0 = wave_add(a0);
-            a1 = wave_add(a1);
-            a2 = wave_add(a2);
-            a3 = wave_add(a3);
-            a4 = wave_add(a4);
-            a5 = wave_add(a5);
-            a6 = wave_add(a6);
-            a7 = wave_add(a7);
-            a8 = wave_add(a8);
-            if (lane == 0) {
-                out[(int64_t)i * 3 + 0] = make_float4(a0, a1, a2, a3);
-                out[(int64_t)i * 3 + 1] = make_float4(a4, a5, a6, a7);
-                out[(int64_t)i * 3 + 2] = make_float4(a8, 0.0f, 0.0f, 0.0f);
-            }
-        }
-    }
+// A target per candidate: candidate b = b0 + bl against image
+// pk = b / group of targets [K][H][W][3], masks [K][H][W] (or null) and the set's
+// weight blocks, wstride floats apart.  pk is wave-uniform, so the three base
+// pointers move on the scalar side; the body is grad_strip_kernel's and a
+// candidate's partials are its bits.
+__global__ void __launch_bounds__(64, 3)
+grad_set_strip_kernel(const float* __restrict__ f9, const int* __restrict__ i4, int64_t S, int64_t b0, int N, int H,
+                      int W, const float* __restrict__ targets, const float* __restrict__ masks, int mode,
+                      float beta, const float* __restrict__ wblocks, int64_t wstride, int group, int nSX,
+                      int nStrips, float4* __restrict__ part) {
+    const int lane = (int)threadIdx.x;
+    const int bl = (int)(blockIdx.x / (unsigned)nStrips);
+    const int strip = (int)(blockIdx.x % (unsigned)nStrips);
+    const int64_t pk = (b0 + bl) / group;
+    const int64_t px = (int64_t)H * W;
+    const float* __restrict__ target = targets + pk * px * 3;
+    const float* __restrict__ mask = masks ? masks + pk * px : nullptr;
+    const double* __restrict__ wsum = reinterpret_cast<const double*>(wblocks + pk * wstride);
+#include "ggs_grad_strip.inc"
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -433,6 +334,108 @@ refine_adam_kernel(float* __restrict__ x, float* __restrict__ m, float* __restri
     x[i] = xi;
 }
 
+// ---- memetic generations of the island group -------------------------
+constexpr int POLISH_PMAX = 512;    // an island's rows are ranked by the counting rank in LDS (the GA's RANKMAX)
+
+// One workgroup per island: the rows of fitness rank j < R (ascending fitness, ties
+// by lower row: the elite list's rank) become refine candidates k * R + j: x and
+// best_x the row's genome, best_fit +inf, rows[k * R + j] the row.
+__global__ void __launch_bounds__(POLISH_PMAX)
+polish_stage_kernel(const float* __restrict__ pop, const float* __restrict__ fits, int P, int N, int R,
+                    int* __restrict__ rows, float* __restrict__ x, float* __restrict__ best_x,
+                    double* __restrict__ best_fit) {
+    __shared__ float key[POLISH_PMAX];
+    __shared__ int top[POLISH_PMAX];
+    const int k = (int)blockIdx.x;
+    const float* __restrict__ f = fits + (int64_t)k * P;
+    for (int r = threadIdx.x; r < P; r += blockDim.x) {
+        key[r] = f[r];
+        top[r] = 0;                         // a valid row whatever the fitness values (NaN ranks collide)
+    }
+    __syncthreads();
+    for (int r = threadIdx.x; r < P; r += blockDim.x) {
+        const float v = key[r];
+        int rank = 0;
+        for (int q = 0; q < P; ++q) rank += (key[q] < v) | ((key[q] == v) & (q < r));
+        if (rank < R) top[rank] = r;
+    }
+    __syncthreads();
+    const int64_t row = (int64_t)N * 9;
+    for (int j = 0; j < R; ++j) {
+        const int64_t c = (int64_t)k * R + j;
+        const float* __restrict__ from = pop + ((int64_t)k * P + top[j]) * row;
+        for (int64_t i = threadIdx.x; i < row; i += blockDim.x) {
+            const float v = from[i];
+            x[c * row + i] = v;
+            best_x[c * row + i] = v;
+        }
+        if (threadIdx.x == 0) {
+            rows[c] = top[j];
+            best_fit[c] = (double)__builtin_inff();
+        }
+    }
+}
+
+// One workgroup per island: candidate k * R + j's best individual and fitness
+// overwrite row rows[k * R + j] iff that fitness is strictly lower than the row's;
+// then the island's elite list from the new fitness vector (the migration's closing
+// step) and the best so far by the GA's rule (the first lowest row, fit + 1e-10 <
+// best in float64).
+__global__ void __launch_bounds__(POLISH_PMAX)
+polish_install_kernel(float* __restrict__ pop, float* __restrict__ fits, int P, int N, int R, int elite_k,
+                      const int* __restrict__ rows, const float* __restrict__ best_x,
+                      const double* __restrict__ best_fit, int* __restrict__ elite, double* __restrict__ gbest_fit,
+                      float* __restrict__ gbest_ind) {
+    __shared__ float key[POLISH_PMAX];
+    __shared__ int from_c[POLISH_PMAX];     // the candidate installed in the row, or -1
+    __shared__ int s_g;
+    const int k = (int)blockIdx.x;
+    float* __restrict__ f = fits + (int64_t)k * P;
+    const int64_t row = (int64_t)N * 9;
+    for (int r = threadIdx.x; r < P; r += blockDim.x) {
+        key[r] = f[r];
+        from_c[r] = -1;
+    }
+    __syncthreads();
+    for (int j = 0; j < R; ++j) {           // the rows are distinct: no order between them
+        const int c = k * R + j, r = rows[c];
+        const float bf = (float)best_fit[c];    // a float32 fitness, widened: exact
+        if (!(bf < key[r])) continue;       // uniform over the workgroup
+        float* __restrict__ to = pop + ((int64_t)k * P + r) * row;
+        const float* __restrict__ src = best_x + (int64_t)c * row;
+        for (int64_t i = threadIdx.x; i < row; i += blockDim.x) to[i] = src[i];
+        __syncthreads();                    // every thread has compared key[r]
+        if (threadIdx.x == 0) {
+            key[r] = bf;
+            f[r] = bf;
+            from_c[r] = c;
+        }
+        __syncthreads();
+    }
+    const int E = elite_k < 1 ? 1 : elite_k;
+    int* __restrict__ el = elite + (int64_t)k * P;
+    for (int r = threadIdx.x; r < P; r += blockDim.x) {
+        const float v = key[r];
+        int rank = 0;
+        for (int q = 0; q < P; ++q) rank += (key[q] < v) | ((key[q] == v) & (q < r));
+        if (rank < E) el[rank] = r;
+    }
+    if (threadIdx.x == 0) {
+        int g = 0;
+        for (int r = 1; r < P; ++r)
+            if (key[r] < key[g]) g = r;
+        s_g = ((double)key[g] + 1e-10 < gbest_fit[k]) ? g : -1;
+    }
+    __syncthreads();
+    const int g = s_g;
+    if (g < 0) return;
+    // an installed row is read from its candidate: the row's own stores are this workgroup's
+    const float* __restrict__ src =
+        from_c[g] >= 0 ? best_x + (int64_t)from_c[g] * row : pop + ((int64_t)k * P + g) * row;
+    for (int64_t i = threadIdx.x; i < row; i += blockDim.x) gbest_ind[(int64_t)k * row + i] = src[i];
+    if (threadIdx.x == 0) gbest_fit[k] = (double)key[g];
+}
+
 }  // namespace
 
 int grad_strips(int H, int W, int* nSX) {
@@ -460,6 +463,48 @@ hipError_t launch_grad(hipStream_t st, const float* genomes, int C, const float*
     const int64_t n = (int64_t)nb * N;
     hipLaunchKernelGGL(grad_finish_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, genomes, C, f9, i4, S,
                        b0, nb, N, H, W, nSX, nStrips / nSX, (const float4*)partials, grad);
+    return hipGetLastError();
+}
+
+hipError_t launch_grad_set(hipStream_t st, const float* genomes, int C, const float* f9, const int* i4, int64_t B,
+                           int64_t b0, int nb, int N, int H, int W, const float* targets, const float* masks,
+                           int mode, float beta, const float* wblocks, int64_t wstride, int group, void* partials,
+                           float* grad) {
+    if (nb <= 0 || N <= 0) return hipSuccess;
+    if (group < 1) return hipErrorInvalidValue;
+    int nSX;
+    const int nStrips = grad_strips(H, W, &nSX);
+    const int64_t S = B * N;
+    hipLaunchKernelGGL(grad_set_strip_kernel, dim3((unsigned)((int64_t)nb * nStrips)), dim3(64), 0, st, f9, i4, S, b0,
+                       N, H, W, targets, masks, mode, beta, wblocks, wstride, group, nSX, nStrips, (float4*)partials);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int64_t n = (int64_t)nb * N;
+    hipLaunchKernelGGL(grad_finish_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, genomes, C, f9, i4, S,
+                       b0, nb, N, H, W, nSX, nStrips / nSX, (const float4*)partials, grad);
+    return hipGetLastError();
+}
+
+int polish_max_population() { return POLISH_PMAX; }
+
+hipError_t launch_polish_stage(hipStream_t st, int K, const float* pop, const float* fits, int P, int N, int R,
+                               int* rows, float* x, float* best_x, double* best_fit) {
+    if (K < 1 || P > POLISH_PMAX || R < 1 || R > P) return hipErrorInvalidValue;
+    int nt = 64;
+    while (nt < P && nt < POLISH_PMAX) nt <<= 1;
+    hipLaunchKernelGGL(polish_stage_kernel, dim3(K), dim3(nt < 256 ? 256 : nt), 0, st, pop, fits, P, N, R, rows, x,
+                       best_x, best_fit);
+    return hipGetLastError();
+}
+
+hipError_t launch_polish_install(hipStream_t st, int K, float* pop, float* fits, int P, int N, int R, int elite_k,
+                                 const int* rows, const float* best_x, const double* best_fit, int* elite,
+                                 double* gbest_fit, float* gbest_ind) {
+    if (K < 1 || P > POLISH_PMAX || R < 1 || R > P) return hipErrorInvalidValue;
+    int nt = 64;
+    while (nt < P && nt < POLISH_PMAX) nt <<= 1;
+    hipLaunchKernelGGL(polish_install_kernel, dim3(K), dim3(nt < 256 ? 256 : nt), 0, st, pop, fits, P, N, R, elite_k,
+                       rows, best_x, best_fit, elite, gbest_fit, gbest_ind);
     return hipGetLastError();
 }
 

@@ -427,6 +427,23 @@ size_t grad_partial_bytes(int N, int H, int W);
 hipError_t launch_grad(hipStream_t st, const float* genomes, int C, const float* f9, const int* i4, int64_t B,
                        int64_t b0, int nb, int N, int H, int W, const float* target, const float* mask, int mode,
                        float beta, const float* wblock, void* partials, float* grad);
+// A target per candidate: candidate b of the batch against image b / group of
+// targets [K][H][W][3] / masks [K][H][W] (or null), wblocks the plan set's weight
+// blocks wstride floats apart.  The rest as launch_grad, whose bits a candidate gets.
+hipError_t launch_grad_set(hipStream_t st, const float* genomes, int C, const float* f9, const int* i4, int64_t B,
+                           int64_t b0, int nb, int N, int H, int W, const float* targets, const float* masks,
+                           int mode, float beta, const float* wblocks, int64_t wstride, int group, void* partials,
+                           float* grad);
+// Memetic generations (ggs_ga_islands_set_polish): island k's R best-ranked rows
+// staged as refine candidates k * R + j (x, best_x, best_fit = +inf, rows), and
+// their refined best installed where strictly lower, the elite lists re-ranked and
+// the islands' best so far updated.  P <= polish_max_population().
+int polish_max_population();
+hipError_t launch_polish_stage(hipStream_t st, int K, const float* pop, const float* fits, int P, int N, int R,
+                               int* rows, float* x, float* best_x, double* best_fit);
+hipError_t launch_polish_install(hipStream_t st, int K, float* pop, float* fits, int P, int N, int R, int elite_k,
+                                 const int* rows, const float* best_x, const double* best_fit, int* elite,
+                                 double* gbest_fit, float* gbest_ind);
 struct RefineStepDev {          // one Adam step's constants (ggs/refine.py adam_step)
     float lr[9];
     float beta1, beta2, eps;

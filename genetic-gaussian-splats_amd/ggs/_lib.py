@@ -63,6 +63,11 @@ class RefineParams(C.Structure):
     _fields_ = [("lr", C.c_float * 9), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float)]
 
 
+class GaPolish(C.Structure):
+    """ggs_ga_polish (include/ggs.h)."""
+    _fields_ = [("every", C.c_int32), ("n_steps", C.c_int32), ("n_rows", C.c_int32), ("adam", RefineParams)]
+
+
 class MaskParams(C.Structure):
     """ggs_mask_params (include/ggs.h)."""
     _fields_ = [("n_scales", C.c_int32), ("edge_scales", C.c_int32 * 4), ("w_edge", C.c_float),
@@ -167,6 +172,15 @@ SIGNATURES = {
                                           C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     "ggs_refine_create": (C.c_int, [C.c_int32, C.POINTER(GaConfig), C.POINTER(RefineParams), _f32p, _f32p, _f32p,
                                     C.c_int32, C.POINTER(C.c_void_p)]),
+    "ggs_fitness_grad_device_planset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float,
+                                                  C.c_void_p, C.c_void_p]),
+    "ggs_fitness_grad_targets": (C.c_int, [_f32p, C.c_int64, C.c_int32, C.c_int32, _f32p, _f32p, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_float,
+                                           _f32p, _f32p]),
+    "ggs_refine_create_targets": (C.c_int, [C.c_int32, C.POINTER(GaConfig), C.POINTER(RefineParams), _f32p, _f32p,
+                                            C.c_int32, _f32p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "ggs_ga_islands_set_polish": (C.c_int, [C.c_void_p, C.POINTER(GaPolish)]),
     "ggs_refine_run": (C.c_int, [C.c_void_p, C.c_int32]),
     "ggs_refine_read": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p]),
     "ggs_refine_destroy": (None, [C.c_void_p]),

@@ -145,29 +145,51 @@ def fitness(genomes_axes, target, H: int, W: int, k_sigma: float = 3.0,
 
 def fitness_grad(genomes_axes, target, H: int, W: int, k_sigma: float = 3.0,
                  weight_mask=None, boost_only: bool = False, boost_beta: float = 1.0,
-                 device=None):
+                 device=None, group: Optional[int] = None):
     """``fitness`` and its gradient with respect to the nine axes-angle genes of
     every splat → (fit float32 [B], grad float32 [B,N,9]); DESIGN.md §8c has the
-    conventions.  ``fit`` has the bits ``fitness`` returns.  One device."""
+    conventions.  ``fit`` has the bits ``fitness`` returns.  One device.
+
+    A 4-D ``target`` [K,H,W,3] (``weight_mask`` [K,H,W] or None) differentiates
+    candidate b against image ``b // group`` in one launch chain (DESIGN.md §8d;
+    ``group`` defaults to B // K); a candidate's bits are those of the call against
+    that image alone."""
     g = _genomes3d(genomes_axes, "fitness_grad")
     B, N, Cc = g.shape
     H, W = int(H), int(W)
     tgt = as_f32(target)
-    if tgt.shape != (H, W, 3):
-        raise GGSInputError(f"target must be [H,W,3] = {(H, W, 3)}, got {tuple(tgt.shape)}")
+    many = tgt.ndim == 4
+    if many:
+        K = tgt.shape[0]
+        if tgt.shape != (K, H, W, 3):
+            raise GGSInputError(f"targets must be [K,H,W,3] = {(K, H, W, 3)}, got {tuple(tgt.shape)}")
+        if group is None:
+            group = max(B // max(K, 1), 1)
+        mshape = (K, H, W)
+    else:
+        if group is not None:
+            raise GGSInputError("group= needs a 4-D target [K,H,W,3]")
+        if tgt.shape != (H, W, 3):
+            raise GGSInputError(f"target must be [H,W,3] = {(H, W, 3)}, got {tuple(tgt.shape)}")
+        mshape = (H, W)
     if weight_mask is None:
         mode, mask_p = _lib.GGS_FIT_NONE, None
     else:
         mask = as_f32(weight_mask)
-        if mask.shape != (H, W):
-            raise GGSInputError(f"weight_mask must be [H,W] = {(H, W)}, got {tuple(mask.shape)}")
+        if mask.shape != mshape:
+            raise GGSInputError(f"weight_mask must be {mshape}, got {tuple(mask.shape)}")
         mode = _lib.GGS_FIT_BOOST if boost_only else _lib.GGS_FIT_WEIGHTED
         mask_p = _fp(mask)
     out = np.empty((B,), np.float32)
     grad = np.empty((B, N, 9), np.float32)
     with _on_devices(device, 1):
-        check(lib.ggs_fitness_grad(_fp(g), B, N, Cc, _fp(tgt), mask_p, mode, float(boost_beta), H, W,
-                                   float(k_sigma), _fp(out), _fp(grad)), "ggs_fitness_grad")
+        if many:
+            check(lib.ggs_fitness_grad_targets(_fp(g), B, N, Cc, _fp(tgt), mask_p, K, int(group), mode,
+                                               float(boost_beta), H, W, float(k_sigma), _fp(out), _fp(grad)),
+                  "ggs_fitness_grad_targets")
+        else:
+            check(lib.ggs_fitness_grad(_fp(g), B, N, Cc, _fp(tgt), mask_p, mode, float(boost_beta), H, W,
+                                       float(k_sigma), _fp(out), _fp(grad)), "ggs_fitness_grad")
     return out, grad
 
 
@@ -293,6 +315,17 @@ class TargetPlanSet:
         check(lib.ggs_fitness_device_planset(self.h, C.c_void_p(stream), C.c_void_p(d_genomes or None), B,
                                              N, Cc, group, float(k_sigma), C.c_void_p(d_out or None)),
               "ggs_fitness_device_planset")
+
+    def fitness_grad(self, stream: int, d_genomes: int, B: int, N: int, Cc: int, group: int, d_targets: int,
+                     d_masks: int, k_sigma: float, d_out: int, d_grad: int) -> None:
+        """Enqueue fitness (d_out [B], may be 0) and gradient (d_grad [B,N,9]) of candidate
+        b against plan ``b // group``.  ``d_targets`` / ``d_masks``: the arrays the set was
+        created from (the set keeps the pixels only in the raster's lane order)."""
+        check(lib.ggs_fitness_grad_device_planset(self.h, C.c_void_p(stream), C.c_void_p(d_genomes or None), B, N,
+                                                  Cc, group, C.c_void_p(d_targets or None),
+                                                  C.c_void_p(d_masks or None), float(k_sigma),
+                                                  C.c_void_p(d_out or None), C.c_void_p(d_grad or None)),
+              "ggs_fitness_grad_device_planset")
 
     def close(self) -> None:
         if getattr(self, "h", None):

@@ -386,6 +386,34 @@ def ring_migration(pops: np.ndarray, fits: np.ndarray, m: int, refit=None):
     return new_p, new_f
 
 
+def polish_elites(pops: np.ndarray, fits: np.ndarray, n_rows: int, refine):
+    """One polish of an island group on the host (the definition the device
+    applies, ``ggs_ga_islands_set_polish`` in include/ggs.h): island k's rows of
+    fitness rank j < ``n_rows`` (ascending fitness, ties by lower row) are handed
+    to ``refine(k, genomes [n_rows, N, 9]) -> (best [n_rows, N, 9], best_fits
+    [n_rows])`` in rank order, and a refined individual and its fitness overwrite
+    the row iff that fitness is strictly lower than the row's; any other row
+    keeps its bits.  ``pops`` [K, P, N, 9], ``fits`` [K, P]; returns new arrays."""
+    pops, fits = np.asarray(pops), np.asarray(fits)
+    if fits.ndim != 2 or pops.ndim != 4 or pops.shape[:2] != fits.shape:
+        raise ValueError(f"pops must be [K, P, N, 9] and fits [K, P], got {pops.shape} and {fits.shape}")
+    K, P = fits.shape
+    n_rows = int(n_rows)
+    if not 1 <= n_rows <= P:
+        raise ValueError(f"n_rows must be in [1, {P}], got {n_rows}")
+    new_p, new_f = pops.copy(), fits.copy()
+    for k in range(K):
+        rows = np.argsort(fits[k], kind="stable")[:n_rows]
+        best, bf = refine(k, pops[k, rows].copy())
+        best = np.asarray(best, pops.dtype).reshape((n_rows,) + pops.shape[2:])
+        bf = np.asarray(bf, fits.dtype).reshape(n_rows)
+        for j, r in enumerate(rows):
+            if bf[j] < fits[k, r]:
+                new_p[k, r] = best[j]
+                new_f[k, r] = bf[j]
+    return new_p, new_f
+
+
 def combine_island_curves(curves: Sequence[Dict[str, Sequence[float]]]) -> Dict[str, List[float]]:
     """An island group's saved curves from the islands' own: per generation,
     ``best`` = min over islands, ``mean`` = mean of the islands' means,
@@ -409,8 +437,19 @@ def genetic_approx(target_img_uint8, H: int, W: int, device, pop_size: int, n_sp
                    init_population: Optional[np.ndarray] = None, progress: bool = True,
                    return_state: bool = False, backend: str = "auto", chunk: int = 50,
                    islands: int = 1, migrate_every: int = 0, migrants: int = 0,
-                   polish_steps: int = 0):
+                   polish_steps: int = 0, memetic_every: int = 0, memetic_steps: int = 0,
+                   memetic_rows: int = 1):
     """algorithm.py:17-195 → (best individual [N, 9] float32, best fitness).
+
+    ``memetic_every`` = M > 0 with ``memetic_steps`` > 0 (device backend only; both
+    default to 0, which changes nothing): after every generation g with g % M == 0
+    each island's ``memetic_rows`` best individuals take ``memetic_steps`` Adam steps
+    on the device gradient (``ggs.refine.DEFAULT_LR``) and replace their row where
+    that lowered the fitness, inside the session and without a host round trip
+    (``ga_device.DeviceGAIslands.set_polish``, ``polish_elites`` is the rule;
+    DESIGN.md §8d).  ``islands=1`` then runs an island group of one, whose
+    trajectory is the single session's.  docs/EXPERIMENTS.md §26 has what was
+    measured; no setting has been tuned.
 
     ``polish_steps`` > 0: after the last generation the best individual is refined
     by that many Adam steps on the device gradient (``ggs.refine.refine`` with its
@@ -447,7 +486,8 @@ def genetic_approx(target_img_uint8, H: int, W: int, device, pop_size: int, n_sp
                                  loss_log_y, seed=seed, draws=draws, evaluate=evaluate,
                                  init_population=init_population, progress=progress,
                                  return_state=return_state, backend=backend, chunk=chunk, islands=islands,
-                                 migrate_every=migrate_every, migrants=migrants)
+                                 migrate_every=migrate_every, migrants=migrants,
+                                 memetic=(int(memetic_every), int(memetic_steps), int(memetic_rows)))
     if int(polish_steps) <= 0:
         return out
     from . import api
@@ -465,18 +505,34 @@ def genetic_approx(target_img_uint8, H: int, W: int, device, pop_size: int, n_sp
     return (best_ind, best_fit) + tuple(out[2:])
 
 
+def _memetic_polish(every: int, steps: int, rows: int):
+    """``DeviceGAIslands.set_polish``'s keyword arguments for the ``memetic_*`` arguments, None when off."""
+    if every < 0 or steps < 0:
+        raise ValueError(f"memetic_every and memetic_steps must be >= 0, got {every} and {steps}")
+    if rows < 1:
+        raise ValueError(f"memetic_rows must be >= 1, got {rows}")
+    return dict(every=every, steps=steps, rows=rows) if every > 0 and steps > 0 else None
+
+
 def _genetic_approx_search(target_img_uint8, H, W, device, pop_size, n_splats, generations, tour_k, elite_k,
                            cxpb, mutpb, mut_sigma_max, mut_sigma_min, schedule, min_scale_splats,
                            max_scale_splats, k_sigma, mask_strength, boost_only, save_video, frame_every,
                            video_dir, prefix, loss_png_path, loss_csv_path, loss_log_y, *, seed, draws,
                            evaluate, init_population, progress, return_state, backend, chunk, islands,
-                           migrate_every, migrants):
+                           migrate_every, migrants, memetic=(0, 0, 1)):
     """``genetic_approx`` without the polish."""
     from .mask import compute_importance_mask, prepare_target
 
     islands = int(islands)
     if islands < 1:
         raise ValueError(f"islands must be >= 1, got {islands}")
+    polish = _memetic_polish(*memetic)
+    if polish is not None:
+        if backend not in ("auto", "host", "device"):
+            raise ValueError(f"backend must be 'host' or 'device', got {backend!r}")
+        if backend == "host" or evaluate is not None or draws is not None:
+            raise ValueError("memetic generations run in the device session: backend='device', no evaluate / "
+                             "draws hooks")
     if islands > 1:
         if backend == "host":
             raise ValueError("islands > 1 needs backend='device': the host backend runs one population")
@@ -504,7 +560,18 @@ def _genetic_approx_search(target_img_uint8, H, W, device, pop_size, n_splats, g
                                       save_video, frame_every, video_dir, prefix, loss_png_path,
                                       loss_csv_path, loss_log_y, seed, None, progress,
                                       return_state, chunk, device,
-                                      islands=(seeds, int(migrate_every), int(migrants)))
+                                      islands=(seeds, int(migrate_every), int(migrants)), polish=polish)
+    if polish is not None:      # an island group of one: the single session's trajectory
+        pop = (np.array(init_population, np.float32, copy=True) if init_population is not None else
+               new_population(pop_size, n_splats, H, W, min_scale_splats, max_scale_splats,
+                              np.random.default_rng(seed)))
+        return _genetic_approx_device(t, imp_mask, pop[None], H, W, generations, tour_k, elite_k, cxpb,
+                                      mutpb, mut_sigma_max, mut_sigma_min, schedule,
+                                      min_scale_splats, max_scale_splats, k_sigma, boost_only,
+                                      save_video, frame_every, video_dir, prefix, loss_png_path,
+                                      loss_csv_path, loss_log_y, seed, None, progress,
+                                      return_state, chunk, device,
+                                      islands=([seed & (2**64 - 1)], 0, 0), polish=polish)
     if evaluate is None:
         from . import api
 
@@ -596,7 +663,9 @@ def genetic_approx_many(images, H: int, W: int, device, pop_size: int, n_splats:
                         mask_strength: float, boost_only: bool, *, seed: Optional[int] = None,
                         migrate_every: int = 0, migrants: int = 0,
                         init_population: Optional[np.ndarray] = None, chunk: int = 50,
-                        progress: bool = True, return_state: bool = False, prep: str = "host"):
+                        progress: bool = True, return_state: bool = False, prep: str = "host",
+                        polish_steps: int = 0, memetic_every: int = 0, memetic_steps: int = 0,
+                        memetic_rows: int = 1):
     """``genetic_approx`` (device backend) for K images in one session: an island
     group with a target per island (``ga_device.DeviceGAIslands`` with a 4-D
     target), one breed and one raster launch per generation for all K.
@@ -612,6 +681,13 @@ def genetic_approx_many(images, H: int, W: int, device, pop_size: int, n_splats:
     on the device (``mask.prepare_targets``, within 2e-5 of the host's; the default
     ``"host"`` keeps every earlier result).
 
+    ``memetic_every`` / ``memetic_steps`` / ``memetic_rows`` are ``genetic_approx``'s
+    (every image's best rows polished against that image, all K in one launch
+    chain).  ``polish_steps`` > 0: after the last generation the K best individuals
+    are refined in ONE session (``ggs_refine_create_targets``, candidate k against
+    image k) and kept where lower; each result equals
+    ``genetic_approx(images[k], ..., polish_steps=...)`` bit for bit.
+
     Returns a list of K ``(best individual [N, 9], best fitness)``; with
     ``return_state`` each entry is ``(best, best_fit, {"population", "fitness",
     "curves"})``.  No frames, CSV or PNG outputs."""
@@ -625,6 +701,8 @@ def genetic_approx_many(images, H: int, W: int, device, pop_size: int, n_splats:
         raise ValueError("genetic_approx_many needs at least one image")
     if prep not in ("host", "device"):
         raise ValueError(f"prep must be 'host' or 'device', got {prep!r}")
+    memetic = (int(memetic_every), int(memetic_steps), int(memetic_rows))
+    polish = _memetic_polish(*memetic)
     seed = resolve_seed(seed)
     seeds = [(seed + k) % 2**64 for k in range(K)]
     if prep == "device":
@@ -665,13 +743,21 @@ def genetic_approx_many(images, H: int, W: int, device, pop_size: int, n_splats:
                                    schedule=schedule, min_scale_splats=min_scale_splats,
                                    max_scale_splats=max_scale_splats, k_sigma=k_sigma,
                                    boost_only=boost_only, chunk=max(1, chunk), on_chunk=on_chunk,
-                                   device=api.device_index(device))
+                                   device=api.device_index(device), polish=polish)
     finally:
         if bar is not None:
             bar.close()
+    refined = None
+    if int(polish_steps) > 0:
+        from .refine import refine
+        refined = refine(st["best"], targets, H, W, int(polish_steps), k_sigma=k_sigma, weight_mask=masks,
+                         boost_only=boost_only, min_scale_splats=min_scale_splats,
+                         max_scale_splats=max_scale_splats, device=api.device_index(device), group=1)
     out = []
     for k in range(K):
         best, bf = st["best"][k], float(st["best_fit"][k])
+        if refined is not None and float(refined["best_fits"][k]) < bf:
+            best, bf = refined["best"][k].copy(), float(refined["best_fits"][k])
         if return_state:
             out.append((best, bf, {"population": st["population"][k], "fitness": st["fitness"][k],
                                    "curves": st["curves"][k]}))
@@ -684,7 +770,7 @@ def _genetic_approx_device(t, imp_mask, pop, H, W, generations, tour_k, elite_k,
                            mut_sigma_max, mut_sigma_min, schedule, min_scale_splats,
                            max_scale_splats, k_sigma, boost_only, save_video, frame_every,
                            video_dir, prefix, loss_png_path, loss_csv_path, loss_log_y, seed,
-                           draws, progress, return_state, chunk, device=None, islands=None):
+                           draws, progress, return_state, chunk, device=None, islands=None, polish=None):
     """genetic_approx with backend="device" (ggs/ga_device.py) on the GPU
     ``device`` names (api.device_index).  ``islands``: (seeds, migrate_every,
     migrants) of an island group, ``pop`` then being [K, P, N, 9]."""
@@ -731,7 +817,7 @@ def _genetic_approx_device(t, imp_mask, pop, H, W, generations, tour_k, elite_k,
                                        schedule=schedule, min_scale_splats=min_scale_splats,
                                        max_scale_splats=max_scale_splats, k_sigma=k_sigma,
                                        boost_only=boost_only, chunk=step, on_chunk=on_chunk,
-                                       device=api.device_index(device))
+                                       device=api.device_index(device), polish=polish)
         else:
             st = run_device_ga(t, imp_mask, pop, generations, tour_k=tour_k, elite_k=elite_k,
                                cxpb=cxpb, mutpb=mutpb, mut_sigma_max=mut_sigma_max,

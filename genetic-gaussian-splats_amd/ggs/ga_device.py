@@ -389,6 +389,25 @@ class DeviceGAIslands:
                      pops.ctypes.data_as(_f32p), C.byref(h)), name)
         self.h = h
 
+    def set_polish(self, every: int, steps: int, rows: int = 1, lr=None, beta1: float = 0.9,
+                   beta2: float = 0.999, eps: float = 1e-8) -> None:
+        """Memetic generations (ggs_ga_islands_set_polish): after every generation g with
+        ``g % every == 0`` (and its migration) each island's ``rows`` best-ranked rows take
+        ``steps`` Adam steps against the island's image and replace the row where strictly
+        better (``ggs.ga.polish_elites`` is the rule).  ``every`` or ``steps`` 0: off.
+        ``lr=None``: ``ggs.refine.DEFAULT_LR``."""
+        if lr is None:
+            from .refine import DEFAULT_LR as lr
+        lr = np.asarray(lr, np.float32).reshape(-1)
+        if lr.shape != (9,):
+            raise _lib.GGSInputError("lr must have nine entries, one per genome column")
+        adam = _lib.RefineParams((C.c_float * 9)(*[float(v) for v in lr]), float(beta1), float(beta2), float(eps))
+        pol = _lib.GaPolish(int(every), int(steps), int(rows), adam)
+        check(lib.ggs_ga_islands_set_polish(self.h, C.byref(pol)), "ggs_ga_islands_set_polish")
+
+    def clear_polish(self) -> None:
+        check(lib.ggs_ga_islands_set_polish(self.h, None), "ggs_ga_islands_set_polish")
+
     def run(self, first_gen: int, n_gens: int, total: int) -> None:
         check(lib.ggs_ga_islands_run(self.h, first_gen, n_gens, total), "ggs_ga_islands_run")
 
@@ -502,11 +521,15 @@ class DeviceDE:
 class DeviceRefine:
     """B candidates refined by Adam on the device (ggs_refine_* in include/ggs.h;
     ``ggs.refine.adam_step`` states the update in numpy).  ``lr``: nine per-column
-    rates."""
+    rates.  A 4-D ``target`` [K, H, W, 3] (``mask`` [K, H, W] or None) refines candidate
+    b against image ``b // group`` in one session (ggs_refine_create_targets; ``group``
+    defaults to B // K); what ``read`` returns for a candidate has the bits of a
+    session on that genome and image alone."""
 
     def __init__(self, target, mask, genomes, *, lr, beta1: float = 0.9, beta2: float = 0.999,
                  eps: float = 1e-8, min_scale_splats: float, max_scale_splats: float,
-                 k_sigma: float = 3.0, boost_only: bool = False, boost_beta: float = 1.0, device: int = 0):
+                 k_sigma: float = 3.0, boost_only: bool = False, boost_beta: float = 1.0, device: int = 0,
+                 group: Optional[int] = None):
         x = _arr(genomes, np.float32)
         if x.ndim == 2:
             x = x[None]
@@ -514,8 +537,15 @@ class DeviceRefine:
             raise _lib.GGSInputError("the device refiner keeps [B, N, 9] genomes")
         B, N, _ = x.shape
         self.target = _arr(target, np.float32)
-        H, W = self.target.shape[:2]
+        many = self.target.ndim == 4
+        if not many and group is not None:
+            raise _lib.GGSInputError("group= needs a 4-D target [K, H, W, 3]")
+        if self.target.ndim not in (3, 4) or self.target.shape[-1] != 3:
+            raise _lib.GGSInputError(f"target must be [H, W, 3] or [K, H, W, 3], got {self.target.shape}")
+        H, W = self.target.shape[-3:-1]
         self.mask = None if mask is None else _arr(mask, np.float32)
+        if self.mask is not None and self.mask.shape != self.target.shape[:-1]:
+            raise _lib.GGSInputError(f"mask must be {self.target.shape[:-1]}, got {self.mask.shape}")
         zero = dict.fromkeys(SIG_KEYS, 0.0)             # the GA's operator fields are not read
         cfg = _config(max(B, 1), N, H, W, 1, 0, 0.0, 0.0, k_sigma, min_scale_splats, max_scale_splats,
                       self.mask, boost_only, boost_beta, "linear", zero, zero, 0)
@@ -526,9 +556,18 @@ class DeviceRefine:
         self.B, self.N, self.H, self.W = B, N, H, W
         h = C.c_void_p()
         # arguments are validated before the library looks for a device
-        check(lib.ggs_refine_create(device, C.byref(cfg), C.byref(prm), self.target.ctypes.data_as(_f32p),
-                                    None if self.mask is None else self.mask.ctypes.data_as(_f32p),
-                                    x.ctypes.data_as(_f32p), B, C.byref(h)), "ggs_refine_create")
+        mask_p = None if self.mask is None else self.mask.ctypes.data_as(_f32p)
+        if many:
+            K = self.target.shape[0]
+            if group is None:
+                group = max(B // max(K, 1), 1)
+            check(lib.ggs_refine_create_targets(device, C.byref(cfg), C.byref(prm),
+                                                self.target.ctypes.data_as(_f32p), mask_p, K,
+                                                x.ctypes.data_as(_f32p), B, int(group), C.byref(h)),
+                  "ggs_refine_create_targets")
+        else:
+            check(lib.ggs_refine_create(device, C.byref(cfg), C.byref(prm), self.target.ctypes.data_as(_f32p),
+                                        mask_p, x.ctypes.data_as(_f32p), B, C.byref(h)), "ggs_refine_create")
         self.h = h
 
     def run(self, n_steps: int) -> None:
@@ -664,15 +703,18 @@ def run_device_ga_islands(target, imp_mask, init_pops, seeds, generations: int, 
                           n_migrants: int, tour_k: int, elite_k: int, cxpb: float, mutpb: float,
                           mut_sigma_max, mut_sigma_min, schedule: str, min_scale_splats: float,
                           max_scale_splats: float, k_sigma: float, boost_only: bool, chunk: int,
-                          on_chunk=None, device: int = 0):
+                          on_chunk=None, device: int = 0, polish: Optional[Dict[str, object]] = None):
     """``run_device_ga`` for an island group (``DeviceGAIslands``).  Migrations are
-    keyed to the generation number, so the result does not depend on ``chunk``."""
+    keyed to the generation number, so the result does not depend on ``chunk``.
+    ``polish``: keyword arguments of ``DeviceGAIslands.set_polish`` (memetic generations)."""
     ga = DeviceGAIslands(target, imp_mask, init_pops, seeds, migrate_every, n_migrants,
                          tour_k=tour_k, elite_k=elite_k, cxpb=cxpb, mutpb=mutpb,
                          mut_sigma_max=mut_sigma_max, mut_sigma_min=mut_sigma_min, schedule=schedule,
                          min_scale_splats=min_scale_splats, max_scale_splats=max_scale_splats,
                          k_sigma=k_sigma, boost_only=boost_only, device=device)
     try:
+        if polish:
+            ga.set_polish(**polish)
         gen = 1
         try:
             while gen <= generations:

@@ -507,6 +507,22 @@ int ggs_fitness_grad_device(int32_t device, void* stream, const float* d_genomes
                             int32_t C, const float* d_target_hw3, const float* d_mask_hw, int32_t mode,
                             float boost_beta, int32_t H, int32_t W, float k_sigma,
                             float* d_out_B, float* d_grad_BN9);
+/* A target per candidate: out and grad of candidate b are the bits
+ * ggs_fitness_grad_device gives it against d_targets_khw3[b / group],
+ * d_masks_khw[b / group] alone.  The plan set keeps the pixels only in the raster's
+ * lane order, so the call also takes the raw arrays the set was created from (the
+ * caller's responsibility); the set supplies the fitness and each image's Sum w.
+ * Rules of ggs_fitness_device_planset (group >= 1, B % group == 0, B / group <= K)
+ * and of ggs_fitness_grad_device, all GGS_EINVAL / GGS_ENOMEM before any device is
+ * touched. */
+int ggs_fitness_grad_device_planset(void* planset, void* stream, const float* d_genomes_axes, int64_t B, int32_t N,
+                                    int32_t C, int32_t group, const float* d_targets_khw3,
+                                    const float* d_masks_khw, float k_sigma, float* d_out_B, float* d_grad_BN9);
+/* host pointers, synchronous, one device: builds its own plan set of the K images */
+int ggs_fitness_grad_targets(const float* genomes_axes, int64_t B, int32_t N, int32_t C,
+                             const float* targets_khw3, const float* masks_khw, int32_t K, int32_t group,
+                             int32_t mode, float boost_beta, int32_t H, int32_t W, float k_sigma,
+                             float* out_B, float* grad_BN9);
 
 /* ---- Adam refiner --------------------------------------------------------------
  * B candidates [B,N,9] refined side by side on the session's own stream.  Step t
@@ -535,6 +551,52 @@ int ggs_refine_run(void* handle, int32_t n_steps);      /* enqueues; no host syn
  * [B,N,9]; fits, best_fits [B].  last_grad: the gradient of the last step run. */
 int ggs_refine_read(void* handle, float* genomes, float* fits, float* best, float* best_fits, float* last_grad);
 void ggs_refine_destroy(void* handle);
+/* K images in one session: targets_khw3 [K,H,W,3], masks_khw [K,H,W] (NULL iff
+ * fitness_mode is GGS_FIT_NONE), one plan set built at create; candidate b is
+ * refined against image b / group (group >= 1, B % group == 0, B / group <= K).
+ * Run, read and destroy are the calls above.  Every array read returns for
+ * candidate b carries the bits of a ggs_refine_create session on that genome and
+ * image alone.  Argument errors as ggs_refine_create and
+ * ggs_fitness_grad_device_planset (GGS_EINVAL / GGS_ENOMEM before any device is
+ * touched). */
+int ggs_refine_create_targets(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p,
+                              const float* targets_khw3, const float* masks_khw, int32_t K,
+                              const float* genomes_BN9, int32_t B, int32_t group, void** handle);
+
+/* ---- memetic generations of an island group ----------------------
+ * After the survivors of every generation g with g % every == 0 (g counts
+ * absolutely, as migrate_every does), and after that generation's migration if
+ * one is due, every island's n_rows best-ranked rows (ascending fitness, ties by
+ * lower row, from the fitness as it stands then) are polished at once: row of
+ * rank j of island k is refine candidate k * n_rows + j, started from the row with
+ * zero moments and t from 1, taken through n_steps steps exactly as ggs_refine_run
+ * takes them and ggs_refine_read's closing evaluation, against island k's image
+ * (the one target of a shared-target group).  The candidate's best individual and
+ * best fitness overwrite the row and its fitness iff that fitness is strictly
+ * lower than the row's; otherwise the row keeps its bits.  A polished row is, bit
+ * for bit, best / best_fits of a refine session started on it; moments do not
+ * survive from one polish to the next.  Then the island's elite list is re-ranked
+ * from the new fitness vector and its best so far updated by the GA's rule
+ * (fit + 1e-10 < best in float64, the first lowest row); curves already written
+ * are not touched.  All of it is enqueued on the session's stream, one prep ->
+ * raster -> finalize -> strip -> finish chain per step for all K * n_rows
+ * candidates, with no host synchronisation.  A generation followed by a polish is
+ * closed unfused, like one followed by a migration (GGS_GA_UNFUSED=1: the same
+ * bits).  A setting holds for the generations run after the call: one already run
+ * and not yet closed is closed first, under the setting it ran with.
+ * every == 0, n_steps == 0 or polish == NULL: off, the session's bits
+ * are those of one that never called this.  The buffers are allocated here.  A
+ * negative field, n_rows outside [1, max(1, elite_k)] and ggs_refine_create's
+ * parameter rules are GGS_EINVAL, a candidate's strip partials above the gradient's
+ * workspace budget GGS_ENOMEM; the session is then left as it was.  ggs/ga.py
+ * polish_elites is the numpy statement the device is held to bit for bit. */
+typedef struct ggs_ga_polish {
+    int32_t every;      /* generations between polishes (absolute count, like migrate_every); 0 = never */
+    int32_t n_steps;    /* Adam steps per polish; 0 = never */
+    int32_t n_rows;     /* best-ranked rows per island, 1 <= n_rows <= max(1, elite_k) */
+    ggs_refine_params adam;
+} ggs_ga_polish;
+int ggs_ga_islands_set_polish(void* handle, const ggs_ga_polish* polish /* NULL = off */);
 
 /* ---- multi-GPU fitness gather -------------------------------
  * One process per GPU; candidates are sharded in contiguous blocks and the only
