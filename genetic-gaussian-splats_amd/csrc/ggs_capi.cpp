@@ -502,8 +502,9 @@ int run_fitness_planned(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B
                           nullptr, group, sw);
 }
 
+// encode: the rows are axes-angle rows, prep encodes them first (GGS_LAYOUT_AXES)
 int run_render(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C, int H, int W,
-               float k, const float bg[3], float* d_img) {
+               float k, const float bg[3], float* d_img, bool encode = false) {
     if (B == 0) return GGS_OK;
     Workspace* w = workspace_for(c, st);
     int rc;
@@ -515,7 +516,7 @@ int run_render(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, 
     if ((rc = ensure_strip_words(w, B, N, H, W, st, &sw))) return rc;
     {
         ProfScope ps(st, 0);
-        GGS_HIP(launch_prep(st, false, d_gen, B * N, C, H, W, k, recs, (int4*)w->bnds.p, nullptr, nullptr, nullptr,
+        GGS_HIP(launch_prep(st, encode, d_gen, B * N, C, H, W, k, recs, (int4*)w->bnds.p, nullptr, nullptr, nullptr,
                             nullptr, 0, sw, N));
     }
     {
@@ -571,6 +572,36 @@ int run_grad_chunks(Workspace* w, hipStream_t st, const float* d_gen, int64_t B,
         else
             GGS_HIP(launch_grad(st, d_gen, C, (const float*)w->gf9.p, (const int*)w->gi4.p, B, b0, nb, N, H, W,
                                 d_targets, d_masks, mode, beta, wblocks, w->gpart.p, d_grad));
+    }
+    return GGS_OK;
+}
+
+// ggs_render_vjp*'s argument errors (GGS_EINVAL) and the workspace budget (GGS_ENOMEM):
+// check_grad_dims' rules without mode and mask, before any device is touched.
+int check_vjp_dims(int64_t B, int32_t N, int32_t C, int32_t layout, int32_t H, int32_t W) {
+    if (layout != GGS_LAYOUT_RENDERER && layout != GGS_LAYOUT_AXES) return fail(GGS_EINVAL, "unknown layout %d", layout);
+    return check_grad_dims(B, N, C, H, W, GGS_FIT_NONE, nullptr);
+}
+
+// The renderer's vector-Jacobian product: prep's stage outputs, then the
+// strip / finish pair per chunk of candidates as run_grad_chunks; no fitness launch
+// and no plan.  d_cot [B][H][W][3], d_grad [B][N][9].
+int run_render_vjp(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C, int layout, int H, int W,
+                   float k, const float bg[3], const float* d_cot, float* d_grad) {
+    Workspace* w = workspace_for(c, st);
+    const size_t per = grad_partial_bytes(N, H, W);     // within the budget: check_vjp_dims
+    const int64_t S = B * N;
+    const int chunk = (int)std::min<int64_t>(B, (int64_t)(kGradChunkBytes / per));
+    int rc;
+    if ((rc = ensure(w->gf9, sizeof(float) * 9 * (size_t)S, st))) return rc;
+    if ((rc = ensure(w->gi4, sizeof(int) * 4 * (size_t)S, st))) return rc;
+    if ((rc = ensure(w->gpart, per * (size_t)chunk, st))) return rc;
+    GGS_HIP(launch_prep(st, layout == GGS_LAYOUT_AXES, d_gen, S, C, H, W, k, nullptr, nullptr, (float*)w->gf9.p,
+                        (int*)w->gi4.p, nullptr));
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = (int)std::min<int64_t>(chunk, B - b0);
+        GGS_HIP(launch_render_vjp(st, layout, d_gen, C, (const float*)w->gf9.p, (const int*)w->gi4.p, B, b0, nb, N, H,
+                                  W, d_cot, bg, w->gpart.p, d_grad));
     }
     return GGS_OK;
 }
@@ -1039,6 +1070,37 @@ int ggs_render_device(int32_t device, void* stream, const float* d_genomes, int6
     return run_render(c, (hipStream_t)stream, d_genomes, B, N, C, H, W, k_sigma, bg ? bg : bg1, d_out_bhw3);
 }
 
+int ggs_render_layout_device(int32_t device, void* stream, const float* d_genomes, int64_t B, int32_t N, int32_t C,
+                             int32_t layout, int32_t H, int32_t W, float k_sigma, const float* bg,
+                             float* d_out_bhw3) {
+    if (layout != GGS_LAYOUT_RENDERER && layout != GGS_LAYOUT_AXES) return fail(GGS_EINVAL, "unknown layout %d", layout);
+    int rc = check_dims(B, N, C, H, W);
+    if (rc) return rc;
+    if (B > 0 && ((!d_genomes && N > 0) || !d_out_bhw3)) return fail(GGS_EINVAL, "null pointer");
+    DevCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    const float bg1[3] = {1.f, 1.f, 1.f};
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    return run_render(c, (hipStream_t)stream, d_genomes, B, N, C, H, W, k_sigma, bg ? bg : bg1, d_out_bhw3,
+                      layout == GGS_LAYOUT_AXES);
+}
+
+int ggs_render_vjp_device(int32_t device, void* stream, const float* d_genomes, int64_t B, int32_t N, int32_t C,
+                          int32_t layout, int32_t H, int32_t W, float k_sigma, const float* bg,
+                          const float* d_cot_bhw3, float* d_grad_BN9) {
+    int rc = check_vjp_dims(B, N, C, layout, H, W);
+    if (rc) return rc;
+    if (!d_genomes || !d_cot_bhw3 || !d_grad_BN9) return fail(GGS_EINVAL, "null genomes/cotangent/grad");
+    DevCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    const float bg1[3] = {1.f, 1.f, 1.f};
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    return run_render_vjp(c, (hipStream_t)stream, d_genomes, B, N, C, layout, H, W, k_sigma, bg ? bg : bg1,
+                          d_cot_bhw3, d_grad_BN9);
+}
+
 }  // extern "C"
 
 namespace ggs {
@@ -1255,6 +1317,34 @@ int ggs_fitness_grad(const float* genomes_axes, int64_t B, int32_t N, int32_t C,
     GGS_HIP(hipMemcpyAsync(out_B, c->out.p, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st));
     GGS_HIP(hipMemcpyAsync(grad_BN9, c->ggrad.p, dbytes, hipMemcpyDeviceToHost, st));
     if (inject_fail_after(1)) return fail(GGS_EHIP, "injected failure after device 1's work (test hook)");
+    return drain.drain();
+}
+
+int ggs_render_vjp(const float* genomes, int64_t B, int32_t N, int32_t C, int32_t layout, int32_t H, int32_t W,
+                   float k_sigma, const float* bg, const float* cot_bhw3, float* grad_BN9, int32_t device) {
+    int rc = check_vjp_dims(B, N, C, layout, H, W);
+    if (rc) return rc;
+    if (!genomes || !cot_bhw3 || !grad_BN9) return fail(GGS_EINVAL, "null genomes/cotangent/grad");
+    DevCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    const float bg1[3] = {1.f, 1.f, 1.f};
+    const size_t vbytes = sizeof(float) * 3 * (size_t)H * W * (size_t)B;
+    const size_t gbytes = sizeof(float) * (size_t)N * C * (size_t)B, dbytes = sizeof(float) * 9 * (size_t)N * (size_t)B;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    hipStream_t st = c->stream;
+    StreamDrain drain;                  // after the context lock: drained on every return
+    // the cotangent is staged in c->out, the render host call's image buffer
+    if ((rc = ensure(c->out, vbytes, st)) || (rc = ensure(c->ggrad, dbytes, st)) || (rc = ensure(c->gen, gbytes, st)))
+        return rc;
+    GGS_HIP(hipStreamSynchronize(st));  // the previous call's work is done with the staging
+    drain.add(c->dev, st);
+    GGS_HIP(hipMemcpyAsync(c->gen.p, genomes, gbytes, hipMemcpyHostToDevice, st));
+    GGS_HIP(hipMemcpyAsync(c->out.p, cot_bhw3, vbytes, hipMemcpyHostToDevice, st));
+    if ((rc = run_render_vjp(c, st, (const float*)c->gen.p, B, N, C, layout, H, W, k_sigma, bg ? bg : bg1,
+                             (const float*)c->out.p, (float*)c->ggrad.p)))
+        return rc;
+    GGS_HIP(hipMemcpyAsync(grad_BN9, c->ggrad.p, dbytes, hipMemcpyDeviceToHost, st));
     return drain.drain();
 }
 

@@ -9,6 +9,9 @@
 //                       through preprocess (render.py:8-47) and encode
 //                       (encode.py:4-59) -> grad [b][s][9]
 //   refine_best_kernel / refine_adam_kernel   the refine session's step
+//   vjp_strip_kernel / vjp_finish_kernel      (§8e) the same pair entered with a cotangent
+//                       dL/d image instead of the fitness: the renderer's vector-
+//                       Jacobian product, for renderer rows or axes-angle rows
 //
 // The forward values the clip decisions hang on (is x inside [0, 1], is exp(.)
 // above 1e-6, ...) are prep's own float32 values: f9 / i4 are launch_prep's stage
@@ -288,6 +291,124 @@ grad_finish_kernel(const float* __restrict__ genomes, int C, const float* __rest
     o[4] = (float)(dsq * ((dvyy - dvxx) * 2.0 * sc + dvxy * ((double)c2 - (double)s2)));
 }
 
+// ---- the renderer's vector-Jacobian product ---------------------------
+// grad_strip_kernel's body entered with a cotangent: g is cot [B][H][W][3] of the
+// absolute candidate b0 + bl (0 where the image clip is active or the pixel is
+// outside the image) and the background is bg0, bg1, bg2 (wave-uniform).
+#define GGS_STRIP_VJP 1
+__global__ void __launch_bounds__(64, 3)
+vjp_strip_kernel(const float* __restrict__ f9, const int* __restrict__ i4, int64_t S, int64_t b0, int N, int H, int W,
+                 const float* __restrict__ cot, float bg0, float bg1, float bg2, int nSX, int nStrips,
+                 float4* __restrict__ part) {
+    const int lane = (int)threadIdx.x;
+    const int bl = (int)(blockIdx.x / (unsigned)nStrips);
+    const int strip = (int)(blockIdx.x % (unsigned)nStrips);
+#include "ggs_grad_strip.inc"
+}
+#undef GGS_STRIP_VJP
+
+// grad_finish_kernel with the rows' layout as a template argument: GGS_LAYOUT_AXES is
+// its arithmetic statement for statement (kept apart so that the pinned code object of
+// grad_finish_kernel stays what it is); GGS_LAYOUT_RENDERER stops the chain at
+// preprocess (render.py:8-47), the rows being the renderer's x, y, log l11, log l22,
+// l21, r, g, b, alpha.  grad [B][N][9].
+template <int LAYOUT>
+__global__ void __launch_bounds__(64)
+vjp_finish_kernel(const float* __restrict__ genomes, int C, const float* __restrict__ f9, const int* __restrict__ i4,
+                  int64_t S, int64_t b0, int nb, int N, int H, int W, int nSX, int nSY,
+                  const float4* __restrict__ part, float* __restrict__ grad) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)nb * N) return;
+    const int bl = (int)(t / N), i = (int)(t % N);
+    const int64_t k = (b0 + bl) * (int64_t)N + i;
+    const int x0 = i4[0 * S + k], x1 = i4[1 * S + k], y0 = i4[2 * S + k], y1 = i4[3 * S + k];
+    const int nStrips = nSX * nSY;
+    double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const int sx0 = clampi(x0 / GS_W, 0, nSX - 1), sx1 = clampi(x1 / GS_W, 0, nSX - 1);
+    const int sy0 = clampi(y0 / GS_H, 0, nSY - 1), sy1 = clampi(y1 / GS_H, 0, nSY - 1);
+    for (int sy = sy0; sy <= sy1; ++sy)
+        for (int sx = sx0; sx <= sx1; ++sx) {
+            if (!strip_hit(x0, x1, y0, y1, sx, sy)) continue;
+            const float4* p = part + (((int64_t)bl * nStrips + (sy * nSX + sx)) * (int64_t)N + i) * 3;
+            const float4 u = p[0], v = p[1], w = p[2];
+            a[0] += (double)u.x;
+            a[1] += (double)u.y;
+            a[2] += (double)u.z;
+            a[3] += (double)u.w;
+            a[4] += (double)v.x;
+            a[5] += (double)v.y;
+            a[6] += (double)v.z;
+            a[7] += (double)v.w;
+            a[8] += (double)w.x;
+        }
+    const double P = f9[2 * S + k], Q = f9[3 * S + k], R = f9[4 * S + k];
+    const double dcx = P * a[0] + Q * a[1], dcy = Q * a[0] + R * a[1];
+    const double dP = -0.5 * a[2], dQ = -a[3], dR = -0.5 * a[4];
+    const double da = a[5], dr = a[6], dg = a[7], db = a[8];
+
+    const float* g = genomes + k * (int64_t)C;
+    float* o = grad + k * 9;
+    // colours and alpha: clip(x, 0, 255) / 255 (render.py:40-43; AXES: encode.py:50-56 clips the same way first)
+    const double dcol[4] = {dr, dg, db, da};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[5 + j] = (g[5 + j] >= 0.0f && g[5 + j] <= 255.0f) ? (float)(dcol[j] / 255.0) : 0.0f;
+    // centre: clip(x, 0, 1) (W - 1) (render.py:15-16)
+    o[0] = (g[0] >= 0.0f && g[0] <= 1.0f) ? (float)(dcx * (double)(W - 1)) : 0.0f;
+    o[1] = (g[1] >= 0.0f && g[1] <= 1.0f) ? (float)(dcy * (double)(H - 1)) : 0.0f;
+
+    if (LAYOUT == GGS_LAYOUT_RENDERER) {
+        // forward values, preprocess_row's own float32 operations
+        const float e11 = det_expf(g[2]), e22 = det_expf(g[3]);
+        const double i11 = (double)ggs_div_rn(1.0f, nmax(e11, EPS6)), i22 = (double)ggs_div_rn(1.0f, nmax(e22, EPS6));
+        const double L21 = g[4], i21 = -L21 * (i11 * i22);
+        // preprocess backward: P = i11^2 + i21^2, Q = i21 i22, R = i22^2, i21 = -l21 i11 i22
+        const double di21 = 2.0 * i21 * dP + i22 * dQ;
+        const double di11 = 2.0 * i11 * dP - L21 * i22 * di21;
+        const double di22 = i21 * dQ + 2.0 * i22 * dR - L21 * i11 * di21;
+        // i = 1 / max(exp(ll), 1e-6): the max passes iff exp(ll) > 1e-6
+        o[2] = e11 > EPS6 ? (float)(-i11 * i11 * di11 * (double)e11) : 0.0f;
+        o[3] = e22 > EPS6 ? (float)(-i22 * i22 * di22 * (double)e22) : 0.0f;
+        o[4] = (float)(-i11 * i22 * di21);
+        return;
+    }
+    // forward values, encode_row's and preprocess_row's own float32 operations
+    const float sxf = det_expf(g[2]), syf = det_expf(g[3]);
+    float sn, cs;
+    det_sincosf(g[4], &sn, &cs);
+    const float sx2 = sxf * sxf, sy2 = syf * syf, c2 = cs * cs, s2 = sn * sn;
+    const float vxx = sx2 * c2 + sy2 * s2;
+    const float vxy = ((sx2 - sy2) * sn) * cs;
+    const float vyy = sx2 * s2 + sy2 * c2;
+    const float l11 = ggs_sqrt_rn(nmax(vxx, EPS12));
+    const float l21 = ggs_div_rn(vxy, l11);
+    const float u22 = vyy - l21 * l21;
+    const float l22 = ggs_sqrt_rn(nmax(u22, EPS12));
+    const float e11 = det_expf(det_logf(l11)), e22 = det_expf(det_logf(l22));
+    const double i11 = (double)ggs_div_rn(1.0f, nmax(e11, EPS6)), i22 = (double)ggs_div_rn(1.0f, nmax(e22, EPS6));
+    const double L21 = l21, i21 = -L21 * (i11 * i22);
+    const double di21 = 2.0 * i21 * dP + i22 * dQ;
+    double di11 = 2.0 * i11 * dP - L21 * i22 * di21;
+    double di22 = i21 * dQ + 2.0 * i22 * dR - L21 * i11 * di21;
+    double dl21 = -i11 * i22 * di21;
+    const double dll11 = e11 > EPS6 ? -i11 * i11 * di11 * (double)e11 : 0.0;
+    const double dll22 = e22 > EPS6 ? -i22 * i22 * di22 * (double)e22 : 0.0;
+    // encode backward
+    double dl11 = dll11 / (double)l11;
+    const double dl22 = dll22 / (double)l22;
+    const double du22 = u22 > EPS12 ? dl22 / (2.0 * (double)l22) : 0.0;     // l22 = sqrt(max(u22, 1e-12))
+    const double dvyy = du22;
+    dl21 += -2.0 * L21 * du22;
+    const double dvxy = dl21 / (double)l11;                                // l21 = vxy / l11
+    dl11 += -dl21 * L21 / (double)l11;
+    const double dvxx = vxx > EPS12 ? dl11 / (2.0 * (double)l11) : 0.0;     // l11 = sqrt(max(vxx, 1e-12))
+    const double sc = (double)sn * (double)cs, dsq = (double)sx2 - (double)sy2;
+    const double dsx2 = dvxx * c2 + dvxy * sc + dvyy * s2;
+    const double dsy2 = dvxx * s2 - dvxy * sc + dvyy * c2;
+    o[2] = (float)(dsx2 * 2.0 * (double)sx2);
+    o[3] = (float)(dsy2 * 2.0 * (double)sy2);
+    o[4] = (float)(dsq * ((dvyy - dvxx) * 2.0 * sc + dvxy * ((double)c2 - (double)s2)));
+}
+
 // ---- refine session -------------------------------------------------------------
 constexpr float PI32 = 3.14159274101257324219f;     // float32(pi)
 constexpr float TWO_PI32 = 6.28318548202514648438f; // float32(2*pi)
@@ -482,6 +603,29 @@ hipError_t launch_grad_set(hipStream_t st, const float* genomes, int C, const fl
     const int64_t n = (int64_t)nb * N;
     hipLaunchKernelGGL(grad_finish_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, genomes, C, f9, i4, S,
                        b0, nb, N, H, W, nSX, nStrips / nSX, (const float4*)partials, grad);
+    return hipGetLastError();
+}
+
+hipError_t launch_render_vjp(hipStream_t st, int layout, const float* genomes, int C, const float* f9, const int* i4,
+                             int64_t B, int64_t b0, int nb, int N, int H, int W, const float* cot, const float bg[3],
+                             void* partials, float* grad) {
+    if (nb <= 0 || N <= 0) return hipSuccess;
+    if (layout != GGS_LAYOUT_RENDERER && layout != GGS_LAYOUT_AXES) return hipErrorInvalidValue;
+    int nSX;
+    const int nStrips = grad_strips(H, W, &nSX);
+    const int64_t S = B * N;
+    hipLaunchKernelGGL(vjp_strip_kernel, dim3((unsigned)((int64_t)nb * nStrips)), dim3(64), 0, st, f9, i4, S, b0, N, H,
+                       W, cot, bg[0], bg[1], bg[2], nSX, nStrips, (float4*)partials);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int64_t n = (int64_t)nb * N;
+    const dim3 grid((unsigned)((n + 63) / 64));
+    if (layout == GGS_LAYOUT_AXES)
+        hipLaunchKernelGGL(vjp_finish_kernel<GGS_LAYOUT_AXES>, grid, dim3(64), 0, st, genomes, C, f9, i4, S, b0, nb, N,
+                           H, W, nSX, nStrips / nSX, (const float4*)partials, grad);
+    else
+        hipLaunchKernelGGL(vjp_finish_kernel<GGS_LAYOUT_RENDERER>, grid, dim3(64), 0, st, genomes, C, f9, i4, S, b0,
+                           nb, N, H, W, nSX, nStrips / nSX, (const float4*)partials, grad);
     return hipGetLastError();
 }
 

@@ -4,6 +4,9 @@
 // text, not as a __device__ function: inlined through a function the same statements
 // are vectorised differently and grad_strip_kernel grows from 144 to 152 VGPRs
 // (DESIGN §8d), and its code object is pinned (tests/test_kernel_resources_grad.py).
+// With GGS_STRIP_VJP defined it is vjp_strip_kernel's body (DESIGN §8e): g is read
+// from the cotangent cot [B][H][W][3] instead of being built from target, mask and
+// mode, and the background is the kernel's bg0, bg1, bg2 instead of white.
     const int sx = strip % nSX, sy = strip / nSX;
     const int64_t base = (b0 + bl) * (int64_t)N;
     const int X = sx * GS_W + (lane & 15);
@@ -13,10 +16,40 @@
 
     // ---- sweep 1: the unclipped final colour ---------------------------------
     float cr[GPL], cg[GPL], cb[GPL];
+#ifdef GGS_STRIP_VJP
+#pragma unroll
+    for (int j = 0; j < GPL; ++j) {                                  // the caller's background
+        cr[j] = bg0;
+        cg[j] = bg1;
+        cb[j] = bg2;
+    }
+#else
 #pragma unroll
     for (int j = 0; j < GPL; ++j) cr[j] = cg[j] = cb[j] = 1.0f;     // fitness.py:15: white background
+#endif
     canvas_upto(f9, i4, S, base, N, N, lane, sx, sy, X, Y0, cr, cg, cb);
 
+#ifdef GGS_STRIP_VJP
+    // ---- g = the cotangent per channel (0 where the image clip is active), S = g . Cf ----
+    const float* __restrict__ V = cot + (b0 + bl) * ((int64_t)H * W * 3);
+    float T[GPL], Sg[GPL], gr[GPL], gg[GPL], gb[GPL];
+#pragma unroll
+    for (int j = 0; j < GPL; ++j) {
+        const int y = Y0 + 4 * j;
+        float r = 0.0f, g = 0.0f, b = 0.0f;
+        if (X < W && y < H) {
+            const int64_t p = (int64_t)y * W + X;
+            r = (cr[j] >= 0.0f && cr[j] <= 1.0f) ? V[3 * p + 0] : 0.0f;
+            g = (cg[j] >= 0.0f && cg[j] <= 1.0f) ? V[3 * p + 1] : 0.0f;
+            b = (cb[j] >= 0.0f && cb[j] <= 1.0f) ? V[3 * p + 2] : 0.0f;
+        }
+        gr[j] = r;
+        gg[j] = g;
+        gb[j] = b;
+        Sg[j] = (r * cr[j] + g * cg[j]) + b * cb[j];
+        T[j] = 1.0f;
+    }
+#else
     // ---- g = dL/dCf per channel (0 where the image clip is active), S = g . Cf ----
     const double hw = (double)H * (double)W;
     double D;
@@ -46,6 +79,7 @@
         Sg[j] = (r * cr[j] + g * cg[j]) + b * cb[j];
         T[j] = 1.0f;
     }
+#endif
 
     // ---- sweep 2: front to back ------------------------------------------------
     float4* const out = part + ((int64_t)bl * nStrips + strip) * (int64_t)N * 3;
@@ -76,8 +110,13 @@
             // float per pixel: u <- (1 - f) u + f (g . c) from u = g . background
             float u[GPL];
             if (exact) {
+#ifdef GGS_STRIP_VJP
+#pragma unroll
+                for (int j = 0; j < GPL; ++j) u[j] = (gr[j] * bg0 + gg[j] * bg1) + opaque(gb[j]) * bg2;
+#else
 #pragma unroll
                 for (int j = 0; j < GPL; ++j) u[j] = (gr[j] + gg[j]) + opaque(gb[j]);
+#endif
                 gdot_canvas_upto(f9, i4, S, base, N, i, lane, sx, sy, X, Y0, gr, gg, gb, u);
             }
             float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f, a8 = 0.f;

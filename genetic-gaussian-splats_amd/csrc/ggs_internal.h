@@ -434,6 +434,13 @@ hipError_t launch_grad_set(hipStream_t st, const float* genomes, int C, const fl
                            int64_t b0, int nb, int N, int H, int W, const float* targets, const float* masks,
                            int mode, float beta, const float* wblocks, int64_t wstride, int group, void* partials,
                            float* grad);
+// The renderer's vector-Jacobian product: grad [B][N][9] = sum over pixels
+// of cot [B][H][W][3] . d image / d rows, the rows in `layout` (GGS_LAYOUT_*), against
+// the background bg (host).  f9 / i4, the candidates b0 .. b0+nb-1 and the partials as
+// launch_grad.
+hipError_t launch_render_vjp(hipStream_t st, int layout, const float* genomes, int C, const float* f9, const int* i4,
+                             int64_t B, int64_t b0, int nb, int N, int H, int W, const float* cot, const float bg[3],
+                             void* partials, float* grad);
 // Memetic generations (ggs_ga_islands_set_polish): island k's R best-ranked rows
 // staged as refine candidates k * R + j (x, best_x, best_fit = +inf, rows), and
 // their refined best installed where strictly lower, the elite lists re-ranked and

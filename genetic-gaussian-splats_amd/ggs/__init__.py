@@ -4,12 +4,14 @@ Plain Python + numpy over libggs.so (hand-written HIP for gfx950, C ABI in
 include/ggs.h).  The drop-in modules with the reference's names live in
 ``modules/`` next to this package.
 """
-from ._lib import (GGS_FIT_BOOST, GGS_FIT_NONE, GGS_FIT_WEIGHTED, GGSDeviceError,  # noqa: F401
-                   GGSError, GGSInputError, LIB_PATH, ensure_init, lib, runtime_info, select_devices)
+from ._lib import (GGS_FIT_BOOST, GGS_FIT_NONE, GGS_FIT_WEIGHTED, GGS_LAYOUT_AXES,  # noqa: F401
+                   GGS_LAYOUT_RENDERER, GGSDeviceError, GGSError, GGSInputError, LIB_PATH, ensure_init, lib,
+                   runtime_info, select_devices)
 from .parallel import RcclGather  # noqa: F401
 from .api import (TargetPlan, TargetPlanSet, as_f32, encode, fitness, fitness_device,  # noqa: F401
                   fitness_grad, fitness_grad_device, fitness_population, preprocess, profile_enable,
-                  profile_read, profile_reset, render, render_device)
+                  profile_read, profile_reset, render, render_device, render_layout_device, render_vjp,
+                  render_vjp_device)
 from .de import differential_evolution  # noqa: F401
 
 __version__ = "0.1.0"

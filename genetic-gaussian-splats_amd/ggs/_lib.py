@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("GGS_LIB", os.path.join(_PKG_ROOT, "libggs.so"))
 
 GGS_OK, GGS_EINVAL, GGS_ENODEV, GGS_EHIP, GGS_ENOMEM = 0, -1, -2, -3, -4
 GGS_FIT_NONE, GGS_FIT_WEIGHTED, GGS_FIT_BOOST = 0, 1, 2
+GGS_LAYOUT_RENDERER, GGS_LAYOUT_AXES = 0, 1
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
@@ -170,6 +171,13 @@ SIGNATURES = {
     "ggs_fitness_grad_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
                                           C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "ggs_render_vjp_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_int32, C.c_float, _f32p, C.c_void_p,
+                                        C.c_void_p]),
+    "ggs_render_vjp": (C.c_int, [_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                 C.c_float, _f32p, _f32p, _f32p, C.c_int32]),
+    "ggs_render_layout_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_float, _f32p, C.c_void_p]),
     "ggs_refine_create": (C.c_int, [C.c_int32, C.POINTER(GaConfig), C.POINTER(RefineParams), _f32p, _f32p, _f32p,
                                     C.c_int32, C.POINTER(C.c_void_p)]),
     "ggs_fitness_grad_device_planset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,

@@ -91,10 +91,23 @@ def _on_devices(device, n_devices: int):
         yield len(ids)
 
 
+_LAYOUTS = {"renderer": _lib.GGS_LAYOUT_RENDERER, "axes": _lib.GGS_LAYOUT_AXES}
+
+
+def layout_id(layout) -> int:
+    """GGS_LAYOUT_* of a layout name ("renderer" / "axes") or of the constant itself."""
+    if isinstance(layout, str) and layout in _LAYOUTS:
+        return _LAYOUTS[layout]
+    if not isinstance(layout, (str, bool)) and layout in _LAYOUTS.values():
+        return int(layout)
+    raise GGSInputError(f"layout must be 'renderer' or 'axes', got {layout!r}")
+
+
 def render(genomes, H: int, W: int, *, k_sigma: float = 3.0,
            background=(1.0, 1.0, 1.0), device=None, n_devices: int = 1,
-           fp16_canvas: bool = False) -> np.ndarray:
-    """render.py:203-252 → float32 [B,H,W,3] in [0,1] (renderer-layout genomes).
+           fp16_canvas: bool = False, layout="renderer") -> np.ndarray:
+    """render.py:203-252 → float32 [B,H,W,3] in [0,1] (renderer-layout genomes;
+    ``layout="axes"``: axes-angle genomes, the render of ``encode(genomes)``).
 
     ``fp16_canvas`` (render.py:213 ``use_fp16_canvas``): the reference's canvas is
     then float16 — the background is stored in half precision, the Triton kernel
@@ -102,6 +115,8 @@ def render(genomes, H: int, W: int, *, k_sigma: float = 3.0,
     nearest even), then clamps and converts back (render.py:234-237, :252).
     Here: background rounded to half, fp32 render, result rounded to half."""
     g = _genomes3d(genomes, "render")
+    if layout_id(layout) == _lib.GGS_LAYOUT_AXES:
+        g = encode(g)
     B, N, Cc = g.shape
     H, W = int(H), int(W)
     out = np.empty((B, H, W, 3), np.float32)
@@ -191,6 +206,38 @@ def fitness_grad(genomes_axes, target, H: int, W: int, k_sigma: float = 3.0,
             check(lib.ggs_fitness_grad(_fp(g), B, N, Cc, _fp(tgt), mask_p, mode, float(boost_beta), H, W,
                                        float(k_sigma), _fp(out), _fp(grad)), "ggs_fitness_grad")
     return out, grad
+
+
+def _background3(background) -> np.ndarray:
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(background, np.float32), (3,)))
+
+
+def render_vjp(genomes, cot, H: int, W: int, *, k_sigma: float = 3.0, background=(1.0, 1.0, 1.0),
+               layout="renderer", device=None) -> np.ndarray:
+    """The renderer's vector-Jacobian product → float32 [B,N,9]:
+    ``sum(cot * d render(genomes) / d genomes[b,s,0:9])`` for a cotangent ``cot``
+    [B,H,W,3] ([H,W,3] for [N,C] genomes), i.e. the gradient of any loss of the
+    image whose ``d loss / d image`` is ``cot``.  ``layout`` names what the rows
+    are ("renderer": ``render``'s input; "axes": axes-angle rows, encoded first).
+    DESIGN.md §8e has the conventions (those of ``fitness_grad``).  One device."""
+    g = _genomes3d(genomes, "render_vjp")
+    B, N, Cc = g.shape
+    H, W = int(H), int(W)
+    lay = layout_id(layout)
+    v = as_f32(cot)
+    if v.ndim == 3 and B == 1:
+        v = v[None]
+    if v.shape != (B, H, W, 3):
+        raise GGSInputError(f"cot must be [B,H,W,3] = {(B, H, W, 3)}, got {tuple(v.shape)}")
+    bg = _background3(background)
+    grad = np.empty((B, N, 9), np.float32)
+    n = _lib.ensure_init()
+    dev = device_index(device)
+    if not 0 <= dev < n:
+        raise _lib.GGSDeviceError(f"device {device!r} -> HIP device {dev}, but {n} visible")
+    check(lib.ggs_render_vjp(_fp(g), B, N, Cc, lay, H, W, float(k_sigma), _fp(bg), _fp(v), _fp(grad), dev),
+          "ggs_render_vjp")
+    return grad
 
 
 def encode(G_axes) -> np.ndarray:
@@ -345,6 +392,23 @@ def render_device(device: int, stream: int, d_genomes: int, B: int, N: int, Cc: 
     check(lib.ggs_render_device(device, C.c_void_p(stream), C.c_void_p(d_genomes), B, N, Cc, H,
                                 W, float(k_sigma), _fp(bg), C.c_void_p(d_out)),
           "ggs_render_device")
+
+
+def render_layout_device(device: int, stream: int, d_genomes: int, B: int, N: int, Cc: int, layout: int, H: int,
+                         W: int, k_sigma: float, d_out: int, background=(1.0, 1.0, 1.0)) -> None:
+    """Enqueue the render of rows in ``layout`` (GGS_LAYOUT_*) on `stream`: layout 0 is ``render_device``."""
+    check(lib.ggs_render_layout_device(device, C.c_void_p(stream), C.c_void_p(d_genomes), B, N, Cc, int(layout), H,
+                                       W, float(k_sigma), _fp(_background3(background)), C.c_void_p(d_out)),
+          "ggs_render_layout_device")
+
+
+def render_vjp_device(device: int, stream: int, d_genomes: int, B: int, N: int, Cc: int, layout: int, H: int,
+                      W: int, k_sigma: float, d_cot: int, d_grad: int, background=(1.0, 1.0, 1.0)) -> None:
+    """Enqueue the render's vector-Jacobian product (d_cot [B,H,W,3] -> d_grad [B,N,9]) on `stream`."""
+    check(lib.ggs_render_vjp_device(device, C.c_void_p(stream), C.c_void_p(d_genomes or None), B, N, Cc, int(layout),
+                                    H, W, float(k_sigma), _fp(_background3(background)),
+                                    C.c_void_p(d_cot or None), C.c_void_p(d_grad or None)),
+          "ggs_render_vjp_device")
 
 
 def profile_enable(on: bool = True) -> None:

@@ -1,4 +1,4 @@
-"""torch.autograd bridge: the splat fitness as a differentiable function.
+"""torch.autograd bridge: the splat fitness and the render as differentiable functions.
 
 ``splat_fitness(genomes, target, mask)`` returns the fitness [B] of [B,N,C]
 axes-angle genomes; ``.backward()`` leaves d fitness / d genomes in
@@ -6,6 +6,12 @@ axes-angle genomes; ``.backward()`` leaves d fitness / d genomes in
 device entry point (ggs_fitness_grad_device) runs on torch's current stream with
 no host copy; CPU tensors go through the host-pointer call.  The gradient is
 computed with the fitness in ``forward`` and only scaled in ``backward``.
+
+``render_splats(genomes, H, W)`` returns the image [B,H,W,3] itself, so that any
+loss written in torch (L1, SSIM, a perceptual network, a crop ...) backpropagates
+into ``genomes.grad``: ``backward`` hands ``grad_output`` to the renderer's
+vector-Jacobian product (ggs_render_vjp_device), again on torch's
+current stream with no host copy.
 
 torch is imported here, never by ``import ggs``.
 """
@@ -75,3 +81,62 @@ def splat_fitness(genomes, target, mask=None, *, k_sigma: float = 3.0, boost_onl
         return SplatFitness.apply(genomes[None], target, mask, float(k_sigma), bool(boost_only),
                                   float(boost_beta))[0]
     return SplatFitness.apply(genomes, target, mask, float(k_sigma), bool(boost_only), float(boost_beta))
+
+
+class RenderSplats(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, genomes, H, W, k_sigma, background, layout):
+        if genomes.dim() != 3 or genomes.shape[2] < 9:
+            raise _lib.GGSInputError(f"genomes must be [B,N,C>=9], got {tuple(genomes.shape)}")
+        B, N, Cc = genomes.shape
+        g = genomes.detach().to(torch.float32).contiguous()
+        if g.is_cuda:
+            dev = g.device
+            img = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+            _lib.ensure_init()
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                api.render_layout_device(dev.index or 0, stream, g.data_ptr(), B, N, Cc, layout, H, W, k_sigma,
+                                         img.data_ptr(), background)
+        else:
+            img = torch.from_numpy(api.render(g, H, W, k_sigma=k_sigma, background=background, layout=layout))
+        ctx.save_for_backward(g)
+        ctx.args = (H, W, k_sigma, background, layout)
+        ctx.in_dtype = genomes.dtype
+        return img.to(genomes.dtype) if genomes.dtype != torch.float32 else img
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        (g,) = ctx.saved_tensors
+        H, W, k_sigma, background, layout = ctx.args
+        B, N, Cc = g.shape
+        v = grad_output.detach().to(torch.float32).contiguous()
+        if g.is_cuda:
+            dev = g.device
+            grad9 = torch.empty((B, N, 9), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                api.render_vjp_device(dev.index or 0, stream, g.data_ptr(), B, N, Cc, layout, H, W, k_sigma,
+                                      v.data_ptr(), grad9.data_ptr(), background)
+        else:
+            grad9 = torch.from_numpy(api.render_vjp(g, v, H, W, k_sigma=k_sigma, background=background,
+                                                    layout=layout))
+        if Cc > 9:
+            grad = torch.zeros((B, N, Cc), dtype=torch.float32, device=grad9.device)
+            grad[:, :, :9] = grad9
+        else:
+            grad = grad9
+        return grad.to(ctx.in_dtype), None, None, None, None, None
+
+
+def render_splats(genomes, H: int, W: int, *, k_sigma: float = 3.0, background=(1.0, 1.0, 1.0),
+                  layout="renderer"):
+    """The image [B,H,W,3] of [B,N,C] genomes ([H,W,3] of [N,C]), differentiable with
+    respect to ``genomes``: ``layout="renderer"`` rows are ``ggs.render``'s
+    input, ``"axes"`` rows are axes-angle genomes.  No gradient reaches ``background``."""
+    bg = tuple(float(x) for x in api._background3(background))
+    args = (int(H), int(W), float(k_sigma), bg, api.layout_id(layout))
+    if genomes.dim() == 2:
+        return RenderSplats.apply(genomes[None], *args)[0]
+    return RenderSplats.apply(genomes, *args)

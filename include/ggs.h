@@ -524,6 +524,38 @@ int ggs_fitness_grad_targets(const float* genomes_axes, int64_t B, int32_t N, in
                              int32_t mode, float boost_beta, int32_t H, int32_t W, float k_sigma,
                              float* out_B, float* grad_BN9);
 
+/* ---- differentiable render -------------------------------------
+ * The renderer's vector-Jacobian product.  With img[b] = clip(blend(preprocess(
+ * rows[b])), 0, 1) against the background bg, exactly what ggs_render_device
+ * writes, and a cotangent cot [B,H,W,3] (d loss / d img of any loss),
+ *   grad[b,s,0:9] = sum over y, x, ch of cot[b,y,x,ch] * d img[b,y,x,ch] / d rows[b,s,0:9]
+ * grad is [B,N,9] whatever the input stride C >= 9.  layout names what the rows
+ * are: GGS_LAYOUT_RENDERER, ggs_render's input (x, y, log l11, log l22, l21, r, g,
+ * b, alpha), or GGS_LAYOUT_AXES, axes-angle rows that encode (encode.py:4-59)
+ * turns into renderer rows first, as the fitness path does.  The derivative's
+ * conventions are those of the fitness gradient above (constant integer AABB,
+ * clip passes iff lo <= x <= hi, max(x, eps) iff x > eps, the image clip per
+ * channel on the unclipped float32 colour); there is no gradient with respect to
+ * bg (host pointer to three floats, NULL = 1, 1, 1).  Deterministic: reruns and
+ * other batches give a candidate the same bits.  One device.  B, N, H or W < 1,
+ * C < 9, B * N >= 2^31, a null genome, cotangent or gradient pointer and an unknown
+ * layout are reported (GGS_EINVAL) before any device is touched; a candidate whose
+ * strip partials exceed the 40 MiB workspace budget is refused with GGS_ENOMEM.
+ * The device call enqueues on `stream` and returns; the host call synchronises
+ * every stream it queued work on before returning, errors included.
+ * ggs_render_layout_device is ggs_render_device with the rows in `layout`: layout
+ * 0 issues ggs_render_device's launches (the same bits), layout 1 gives the bits
+ * of ggs_render on ggs_encode's rows. */
+#define GGS_LAYOUT_RENDERER 0
+#define GGS_LAYOUT_AXES 1
+int ggs_render_vjp_device(int32_t device, void* stream, const float* d_genomes, int64_t B, int32_t N, int32_t C,
+                          int32_t layout, int32_t H, int32_t W, float k_sigma, const float* bg /* host, NULL = 1,1,1 */,
+                          const float* d_cot_bhw3, float* d_grad_BN9);
+int ggs_render_vjp(const float* genomes, int64_t B, int32_t N, int32_t C, int32_t layout, int32_t H, int32_t W,
+                   float k_sigma, const float* bg, const float* cot_bhw3, float* grad_BN9, int32_t device);
+int ggs_render_layout_device(int32_t device, void* stream, const float* d_genomes, int64_t B, int32_t N, int32_t C,
+                             int32_t layout, int32_t H, int32_t W, float k_sigma, const float* bg, float* d_out_bhw3);
+
 /* ---- Adam refiner --------------------------------------------------------------
  * B candidates [B,N,9] refined side by side on the session's own stream.  Step t
  * (from 1) evaluates fitness and gradient g of the state x_t, makes x_t the
