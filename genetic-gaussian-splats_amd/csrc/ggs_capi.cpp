@@ -141,6 +141,7 @@ struct Workspace {
     DevBuf swords, smasks;            // strip words and masks, prep -> raster (StripWords)
     DevBuf gf9, gi4, gpart, gout;     // fitness gradient: prep's stage outputs, strip partials, unwanted fitness
     int order_H = -1, order_W = -1;   // (H, W) the tile order was built for
+    bool strips_ok = false;           // ... and whether its strip table holds that canvas
     uint64_t plan_key = 0;            // inputs the plan was built from (0: none / volatile)
 };
 
@@ -149,8 +150,11 @@ int ensure_tile_order(Workspace* w, int H, int W, hipStream_t st) {
     if (w->order_H == H && w->order_W == W) return GGS_OK;
     const int n = raster_order_len(H, W);
     int rc;
-    if ((rc = ensure(w->order, sizeof(int) * (size_t)n, st))) return rc;
-    std::vector<int> h(n);
+    // the order's n groups, then the same n groups as decoded strips (strip_table_entry:
+    // the strip-words raster's table; zeros where the canvas does not fit its fields,
+    // launch_raster then never reads them)
+    if ((rc = ensure(w->order, sizeof(int) * 2 * (size_t)n, st))) return rc;
+    std::vector<int> h(2 * (size_t)n);
     raster_tile_order(H, W, h.data());
 #ifdef GGS_PROBE_BUILD
     // probe: a dispatch order from a file of n int32 group indices (order experiments)
@@ -163,8 +167,13 @@ int ensure_tile_order(Workspace* w, int H, int W, hipStream_t st) {
         fclose(fp);
     }
 #endif
+    int nTX;
+    raster_tiles(H, W, &nTX);
+    w->strips_ok = true;
+    for (int g = 0; g < n; ++g)
+        if (!strip_table_entry(h[g], nTX, &h[(size_t)n + g])) w->strips_ok = false;
     GGS_HIP(hipStreamSynchronize(st));
-    GGS_HIP(hipMemcpy(w->order.p, h.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+    GGS_HIP(hipMemcpy(w->order.p, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice));
     w->order_H = H;
     w->order_W = W;
     return GGS_OK;
@@ -441,6 +450,9 @@ int ensure_strip_words(Workspace* w, int64_t B, int N, int H, int W, hipStream_t
     if ((rc = ensure(w->smasks, strip_masks_bytes(B, N, H, W), st))) return rc;
     sw->words = (int*)w->swords.p;
     sw->masks = (uint64_t*)w->smasks.p;
+    // the strip table of the workspace's tile order (ensure_tile_order(w, H, W) came first)
+    if (w->order_H == H && w->order_W == W && w->strips_ok)
+        sw->table = (const int*)w->order.p + raster_order_len(H, W);
     return GGS_OK;
 }
 int run_fitness_planned(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C,

@@ -59,7 +59,125 @@ static_assert(sizeof(SplatRec) == 64, "SplatRec must be 64 bytes");
 struct StripWords {
     int* words = nullptr;         // strip_words_bytes
     uint64_t* masks = nullptr;    // strip_masks_bytes
+    const int* table = nullptr;   // the canvas's strip table (strip_table_entry per dispatch group)
 };
+
+// ---- the strip-words raster's launch descriptor ---------------------------------
+// Every strip wave of a launch used to derive its (candidate, strip) from the
+// block index with three runtime divisions and a chain of argument loads, on
+// identical inputs.  The host does that once per launch: the divisions become
+// multiply-shifts by constants it builds, and the dispatch-order table carries
+// the decoded strip.
+//
+// n / d == ((uint64_t)n * mul) >> shift for every n <= the nmax it was built for.
+struct GridDiv {
+    uint32_t mul = 0, shift = 0;   // (0, 0): the quotient 0
+};
+__host__ __device__ inline uint32_t grid_div(uint32_t n, GridDiv g) {
+    return (uint32_t)(((uint64_t)n * g.mul) >> g.shift);
+}
+// Round-up magic: mul = ceil(2^k / d) at the smallest k whose error e = mul * d - 2^k
+// satisfies e * nmax < 2^k.  (mul n / 2^k = n / d + e n / (d 2^k): the floor is that
+// of n / d while the excess stays below 1 / d, the least distance of n / d to the
+// next integer.)  k = 31 + ceil(log2 d) always does for nmax < 2^31, with mul < 2^32.
+// False: no 32-bit constant is exact up to nmax (or d == 0).
+inline bool grid_div_make(uint32_t d, uint32_t nmax, GridDiv* out) {
+    if (d == 0) return false;
+    for (uint32_t k = 0; k < 64; ++k) {
+        const uint64_t p = (uint64_t)1 << k;
+        const uint64_t m = p / d + (p % d != 0);
+        if (m >> 32) break;
+        const uint64_t e = m * d - p;                 // < d: e * nmax fits 64 bits
+        if (e * (uint64_t)nmax < p) {
+            out->mul = (uint32_t)m;
+            out->shift = k;
+            return true;
+        }
+    }
+    return false;
+}
+// One entry of the strip table: dispatch group grp (raster_tile_order's numbering,
+// tile * 4 + strip of the tile) as the strip's column index over the canvas,
+// tx * 4 + strip (bits 0-15; its low two bits are the strip of the tile) and the
+// row tile ty (bits 16-30).  False: the canvas has more strips than the fields hold.
+constexpr int kStripsPerTile = 4;
+inline bool strip_table_entry(int grp, int nTX, int* out) {
+    const int t = grp / kStripsPerTile, s = grp % kStripsPerTile;
+    const int cs = (t % nTX) * kStripsPerTile + s, ty = t / nTX;
+    if (cs > 0xFFFF || ty > 0x7FFF) return false;
+    *out = cs | (ty << 16);
+    return true;
+}
+__host__ __device__ inline int strip_entry_column(int e) { return e & 0xFFFF; }   // tx * 4 + strip of the tile
+__host__ __device__ inline int strip_entry_row(int e) { return e >> 16; }         // ty
+// The by-value block that is raster_kernel's first argument and all that the
+// strip-words instances, raster_kernel<MODE, false, false>, read (launch_raster
+// fills it).  The grid decode's fields come first.
+struct StripLaunch {
+    const int* table = nullptr;        // strip_table_entry per dispatch group
+    const uint64_t* masks = nullptr;   // StripWords
+    const int* words = nullptr;
+    // blocks [flip_lo, flip_lo + flip_n) run as block flip_sum - index (the single-round
+    // boustrophedon; flip_n = 0: none)
+    uint32_t flip_lo = 0, flip_n = 0, flip_sum = 0;
+    // candidate chunks: chunk c = index / per has chunk_b candidates (the last one
+    // last_b), c * chunk_b being its first; one chunk: per_div = (0, 0), c_last = 0
+    uint32_t per = 0, c_last = 0, chunk_b = 0, last_b = 0;
+    GridDiv per_div, chunk_div, last_div;
+    int N = 0, ncols = 0;              // splats per candidate; column strips of the canvas (4 nTX)
+    int ncp = 0;                       // strip_mask_chunks(N)
+    int words_b = 0, masks_b = 0;      // per candidate: ints of words (nTY N), mask words ((2 ncols + nTY) ncp)
+    int nslots = 0;                    // strips per candidate (4 nTiles)
+    const SplatRec* recs = nullptr;
+    const float4* plan = nullptr;      // MODE 1
+    float* partials = nullptr;
+    float* img = nullptr;              // MODE 0
+    int H = 0, W = 0;
+    float bg_r = 0.f, bg_g = 0.f, bg_b = 0.f;
+};
+// Fills the grid decode of a launch of B candidates over nTiles tiles in chunks of CH
+// (raster_chunk) on a device of `simds` SIMDs.  False: some constant does not exist
+// (the launch then goes to the instance that divides).
+inline bool strip_launch_grid(int64_t B, int nTiles, int CH, int simds, StripLaunch* d) {
+    const int64_t nG = (int64_t)nTiles * kStripsPerTile, grid = B * nG;
+    if (B <= 0 || nG <= 0 || CH <= 0 || grid >= ((int64_t)1 << 31)) return false;
+    d->flip_lo = d->flip_n = d->flip_sum = 0;
+    if (simds > 0 && grid > 2 * (int64_t)simds && grid <= 3 * (int64_t)simds) {
+        d->flip_lo = (uint32_t)simds;
+        d->flip_n = (uint32_t)simds;
+        d->flip_sum = 3u * (uint32_t)simds - 1u;
+    }
+    const bool chunks = B > CH;
+    const int64_t c_last = chunks ? (B - 1) / CH : 0;
+    d->per = chunks ? (uint32_t)(CH * nG) : 0u;
+    d->c_last = (uint32_t)c_last;
+    d->chunk_b = (uint32_t)(chunks ? CH : B);
+    d->last_b = (uint32_t)(B - c_last * CH);
+    d->per_div = GridDiv{};
+    if (chunks && !grid_div_make(d->per, (uint32_t)(grid - 1), &d->per_div)) return false;
+    // dividends: a block's index in its chunk, then (its remainder + its group), below b + nG
+    const int64_t in_chunk = (chunks ? (int64_t)d->per : grid) - 1;
+    const auto lim = [&](uint32_t b) {
+        const int64_t x = (int64_t)b + nG - 2;
+        return (uint32_t)(x > in_chunk ? x : in_chunk);
+    };
+    return grid_div_make(d->chunk_b, lim(d->chunk_b), &d->chunk_div) &&
+           grid_div_make(d->last_b, lim(d->last_b), &d->last_div);
+}
+// The candidate and dispatch group of block `index` (device and host: the tests
+// restate today's divisions against it).
+struct StripBlock { uint32_t b, group; };
+__host__ __device__ inline StripBlock strip_launch_block(const StripLaunch& d, uint32_t index) {
+    if (index - d.flip_lo < d.flip_n) index = d.flip_sum - index;
+    const uint32_t c = grid_div(index, d.per_div);
+    index -= c * d.per;
+    const bool last = c == d.c_last;
+    const uint32_t nb = last ? d.last_b : d.chunk_b;
+    const GridDiv dv = last ? d.last_div : d.chunk_div;
+    const uint32_t gi = grid_div(index, dv);
+    const uint32_t x = index - gi * nb + gi;           // (index + gi) mod nb == x mod nb
+    return {c * d.chunk_b + (x - grid_div(x, dv) * nb), gi};
+}
 bool strip_words_ok(int N);       // N % 64 == 0 and at most the no-saturation-check limit
 size_t strip_words_bytes(int64_t B, int N, int H, int W);
 size_t strip_masks_bytes(int64_t B, int N, int H, int W);

@@ -311,7 +311,10 @@ __device__ __forceinline__ void strip_done(const FinFused& fin, const float* par
 #if GGS_TIMING
 constexpr int GGS_TIMING_WAVES = 1 << 16;
 // per wave (blockIdx, WPB = 1): realtime start, realtime end (100 MHz), cull,
-// visit and epilogue shader clocks, HW_ID | XCC_ID << 24, listed visits, blended visits
+// visit and epilogue shader clocks, HW_ID | XCC_ID << 32 | entry clocks << 40 (the
+// part of the cull clocks before the strip-words cull issues its first load, 24
+// bits, saturating; 0 in the instances that cull from the bounds), listed visits,
+// blended visits
 __device__ unsigned long long g_ggs_timing[8 * GGS_TIMING_WAVES];
 #define GGS_TMARK(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
 #else
@@ -431,7 +434,7 @@ raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, in
             const int* __restrict__ tile_order, const unsigned char* __restrict__ dirty,
             const float* __restrict__ clean, const int* __restrict__ live, int CH, FinFused fin, int simds,
             int group, const int* __restrict__ plan_of = nullptr, const int* __restrict__ swords = nullptr,
-            const uint64_t* __restrict__ smasks = nullptr) {
+            const uint64_t* __restrict__ smasks = nullptr, const StripLaunch* __restrict__ sl = nullptr) {
     static_assert(!MULTI || MODE == 1, "plan sets are for the fitness epilogue");
     static_assert(!LIST || MULTI, "a plan list names plans of a plan set");
     constexpr bool DS = GGS_DEPTH_SPLIT && MODE == 1 && !SAT;
@@ -444,7 +447,7 @@ raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, in
     const int lane = threadIdx.x & 63;
 #if GGS_TIMING
     const unsigned long long rt_start = __builtin_amdgcn_s_memrealtime();
-    unsigned long long t_cull = 0, t_vis = 0, t_mark = __builtin_amdgcn_s_memtime();
+    unsigned long long t_cull = 0, t_vis = 0, t_entry = 0, t_mark = __builtin_amdgcn_s_memtime();
     unsigned n_vis = 0, n_done = 0;     // listed / blended visits
 #endif
 #if GGS_DEPTH_SPLIT
@@ -453,55 +456,75 @@ raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, in
 #else
     const int wib = ufirst((int)(threadIdx.x >> 6));  // wave in block (uniform: keeps control on SALU)
 #endif
-    // SA loop rounds: the grid is sized for the session's capacity and only the
-    // first *live candidates are evaluated; the grid order below is then that of
-    // a launch over *live candidates, and the blocks past it exit at once
-    if (live) {
-        B = ufirst(*live);
-        if ((int64_t)blockIdx.x >= (int64_t)B * nTiles * SPB) return;
+    // this wave's candidate b, tile t and strip wv of the tile (columns from tx0, rows from ty0)
+    int b, t, wv, tx0, ty0;
+    [[maybe_unused]] int scol = 0, srow = 0;   // PRE: the strip's column index over the canvas, its row tile
+    if constexpr (PRE) {
+        // the strip-words instances: the grid decode below as the host prepared it
+        // (StripLaunch): multiply-shifts for its divisions, and a table entry that
+        // is the decoded strip.  No live count, dirty strips or plan set reach them
+        // (launch_raster).  t is not formed: t * 4 + wv == srow * ncols + scol.
+        static_assert(WPB == 1 && SPB == kStripsPerTile, "strip_table_entry's numbering");
+        const StripBlock sb = strip_launch_block(*sl, blockIdx.x);
+        const int e = sl->table[sb.group];
+        b = (int)sb.b;
+        scol = strip_entry_column(e);
+        srow = strip_entry_row(e);
+        t = 0;
+        wv = scol & (kStripsPerTile - 1);
+        tx0 = (scol >> 2) * TILE;
+        ty0 = srow * TILE_H;
+    } else {
+        // SA loop rounds: the grid is sized for the session's capacity and only the
+        // first *live candidates are evaluated; the grid order below is then that of
+        // a launch over *live candidates, and the blocks past it exit at once
+        if (live) {
+            B = ufirst(*live);
+            if ((int64_t)blockIdx.x >= (int64_t)B * nTiles * SPB) return;
+        }
+        // strip-major grid: B consecutive blocks run one strip (group) for every
+        // candidate; groups go central (heavy) first to shorten the grid's tail.
+        // Large launches run in candidate chunks of CH (all groups of one chunk, then
+        // the next), so a chunk's records stay cached while its groups run
+        int idx = blockIdx.x, b0 = 0, Bc = B;
+        // A launch of 2-3 strip-waves per SIMD runs in one round: every wave is
+        // resident from the start and the three sharing a SIMD (blocks r, r + S,
+        // r + 2S, S = SIMDs) split its VALU, so the SIMD ends with the SUM of their
+        // work (docs/EXPERIMENTS.md §14).  The middle third runs reversed: the
+        // heaviest (central) strips then share a SIMD with the lightest of the
+        // middle third instead of its heaviest (a boustrophedon over the expected
+        // cost order; the bits do not depend on the order).  Shipped GA launch
+        // (24 x 128 strips) raster -1.45 %; with two waves per SIMD (a lone 2048^2
+        // SA neighbour) the pairing measured +1.05 %, so only above 2S (EXP §15)
+        if (simds > 0) {
+            const int n = B * nTiles * SPB;
+            if (n > 2 * simds && n <= 3 * simds && idx >= simds && idx < 2 * simds) idx = 3 * simds - 1 - idx;
+        }
+        if (B > CH) {
+            const int per = CH * nTiles * SPB;
+            const int c = idx / per;
+            idx -= c * per;
+            b0 = c * CH;
+            Bc = min(CH, B - b0);
+        }
+        const int gi = idx / Bc;
+        const int grp = tile_order ? tile_order[gi] : gi;
+        // candidates rotate by one per group: with B % 8 == 0 a fixed b would stay on
+        // one XCD (blocks go round-robin to the 8 XCDs) and per-XCD work would be the
+        // sum of 16 candidates' costs (tools/probe/wave_timing.py: XCD end times 197-207 us)
+        // ... for the large-N instances only every 2^XCD_SHIFT groups: blocks B apart
+        // (the next group's block in the same XCD slot) then run the same candidate,
+        // whose records stay in that XCD's caches across 8 groups (see XCD_SHIFT)
+        b = b0 + (int)((idx + (gi >> (SAT ? XCD_SHIFT : 0))) % Bc);
+        t = grp / SPB;
+        wv = (grp % SPB) * WPB + wib;           // strip 0..3 of the tile
+        tx0 = (t % nTX) * TILE;
+        ty0 = (t / nTX) * TILE_H;
     }
-    // strip-major grid: B consecutive blocks run one strip (group) for every
-    // candidate; groups go central (heavy) first to shorten the grid's tail.
-    // Large launches run in candidate chunks of CH (all groups of one chunk, then
-    // the next), so a chunk's records stay cached while its groups run
-    int idx = blockIdx.x, b0 = 0, Bc = B;
-    // A launch of 2-3 strip-waves per SIMD runs in one round: every wave is
-    // resident from the start and the three sharing a SIMD (blocks r, r + S,
-    // r + 2S, S = SIMDs) split its VALU, so the SIMD ends with the SUM of their
-    // work (docs/EXPERIMENTS.md §14).  The middle third runs reversed: the
-    // heaviest (central) strips then share a SIMD with the lightest of the
-    // middle third instead of its heaviest (a boustrophedon over the expected
-    // cost order; the bits do not depend on the order).  Shipped GA launch
-    // (24 x 128 strips) raster -1.45 %; with two waves per SIMD (a lone 2048^2
-    // SA neighbour) the pairing measured +1.05 %, so only above 2S (EXP §15)
-    if (simds > 0) {
-        const int n = B * nTiles * SPB;
-        if (n > 2 * simds && n <= 3 * simds && idx >= simds && idx < 2 * simds) idx = 3 * simds - 1 - idx;
-    }
-    if (B > CH) {
-        const int per = CH * nTiles * SPB;
-        const int c = idx / per;
-        idx -= c * per;
-        b0 = c * CH;
-        Bc = min(CH, B - b0);
-    }
-    const int gi = idx / Bc;
-    const int grp = tile_order ? tile_order[gi] : gi;
-    // candidates rotate by one per group: with B % 8 == 0 a fixed b would stay on
-    // one XCD (blocks go round-robin to the 8 XCDs) and per-XCD work would be the
-    // sum of 16 candidates' costs (tools/probe/wave_timing.py: XCD end times 197-207 us)
-    // ... for the large-N instances only every 2^XCD_SHIFT groups: blocks B apart
-    // (the next group's block in the same XCD slot) then run the same candidate,
-    // whose records stay in that XCD's caches across 8 groups (see XCD_SHIFT)
-    const int b = b0 + (int)((idx + (gi >> (SAT ? XCD_SHIFT : 0))) % Bc);
     // a plan set: the candidate's plan, divided here (the division's VALU temporaries
     // would spill at the epilogue's register peak) and kept in one SGPR
     // (LIST, the SA chain groups: the plan is named by a list, one scalar load)
     const int pk = LIST ? ufirst(plan_of[b]) : MULTI ? ufirst(b / group) : 0;
-    const int t = grp / SPB;
-    const int wv = (grp % SPB) * WPB + wib;           // strip 0..3 of the tile
-    const int tx0 = (t % nTX) * TILE;
-    const int ty0 = (t / nTX) * TILE_H;
     const int ty1 = min(ty0 + TILE_H, H) - 1;
     if (MODE != 0 && dirty) {         // incremental (SA): a strip no changed splat touches
         const int64_t slot = ((int64_t)b * nTiles + t) * 4 + wv;   // keeps the current state's
@@ -624,13 +647,17 @@ raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, in
             // is prep's row half with the clip bit from the clip mask.  One batch:
             // N <= SAT_MIN_SPLATS <= LIMIT.
             static_assert(SAT_MIN_SPLATS <= LIMIT, "strip words: the whole cull is one batch");
-            const int nch = N >> 6, ncp = strip_mask_chunks(N), nTY = (H + TILE_H - 1) / TILE_H, nCS = nTX * 4;
-            const int ty = t / nTX;
-            const int* __restrict__ rw = swords + ((int64_t)b * nTY + ty) * N;
-            const uint64_t* __restrict__ mhit = smasks + ((int64_t)b * (2 * nCS + nTY) + (sx0 >> 4)) * ncp;
+            // (the per-candidate strides, the mask row length and the strip's column and
+            // row come with the launch: StripLaunch, no division here)
+            const int nch = N >> 6, ncp = sl->ncp, nCS = sl->ncols;
+            const int* __restrict__ rw = swords + ((int64_t)b * sl->words_b + srow * N);
+            const uint64_t* __restrict__ mhit = smasks + ((int64_t)b * sl->masks_b + scol * ncp);
             const uint64_t* __restrict__ mclip = mhit + (int64_t)nCS * ncp;
-            const uint64_t* __restrict__ mrow = mhit + (int64_t)(2 * nCS + ty - (sx0 >> 4)) * ncp;
+            const uint64_t* __restrict__ mrow = mhit + (int64_t)(2 * nCS + srow - scol) * ncp;
             for (int c0 = 0; c0 < nch; c0 += 4) {
+#if GGS_TIMING
+                if (c0 == 0) { GGS_TMARK(now); t_entry = now - t_mark; }
+#endif
                 const int i0 = N - 1 - 64 * c0 - lane;      // chunks past N: a clamped load, an empty mask
                 int w0 = rw[i0], w1 = rw[max(i0 - 64, 0)], w2 = rw[max(i0 - 128, 0)], w3 = rw[max(i0 - 192, 0)];
                 uint64_t a0 = mhit[c0], a1 = mhit[c0 + 1], a2 = mhit[c0 + 2], a3 = mhit[c0 + 3];
@@ -1062,7 +1089,10 @@ raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, in
         // (the set's strips are numbered through, pk * nTiles * 4 + the plan's own:
         // the single plan's address arithmetic)
         if (MULTI) fin.wpartials += (int64_t)pk * plan_wsum_floats(nTiles);
-        const float4* __restrict__ P = plan + (int64_t)((MULTI ? pk * nTiles + t : t) * 4 + wv) * RG * 64 + lane;
+        // the strip's number over the canvas, t * 4 + wv (PRE: from the table entry)
+        const int tw = PRE ? srow * sl->ncols + scol : t * 4 + wv;
+        const float4* __restrict__ P =
+            plan + (int64_t)(PRE ? tw : (MULTI ? pk * nTiles + t : t) * 4 + wv) * RG * 64 + lane;
         f2_t accp = 0.0f;
         // background pairs (bg, bg) in SGPR pairs: no VGPRs at the epilogue's peak
         const uint64_t bg2r = (uint64_t)__float_as_uint(bg_r) * 0x100000001ull;
@@ -1092,7 +1122,8 @@ raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, in
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
         if (lane == 0)        // one partial per (candidate, tile, strip): no block barrier
-            store_partial(partials + ((int64_t)b * nTiles + t) * 4 + wv, acc, FUSED);
+            store_partial(partials + (PRE ? (int64_t)b * sl->nslots + tw : ((int64_t)b * nTiles + t) * 4 + wv), acc,
+                          FUSED);
         if (FUSED) strip_done(fin, partials, b, nTiles * 4, lane);
     }
 #if GGS_TIMING
@@ -1103,28 +1134,35 @@ raster_body(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, in
             unsigned long long* o = g_ggs_timing + 8 * (size_t)blockIdx.x;
             o[0] = rt_start; o[1] = rt_end; o[2] = t_cull; o[3] = t_vis; o[4] = now - t_mark;
             o[5] = (unsigned long long)__builtin_amdgcn_s_getreg(0xF804) |
-                   ((unsigned long long)__builtin_amdgcn_s_getreg(0xF814) << 32);
+                   ((unsigned long long)(__builtin_amdgcn_s_getreg(0xF814) & 0xFu) << 32) |
+                   ((t_entry < 0xFFFFFFull ? t_entry : 0xFFFFFFull) << 40);
             o[6] = n_vis; o[7] = n_done;
         }
     }
 #endif
 }
 
+// The instances with visit words compact prep's strip words (launch_raster hands
+// batches without them to bounds_cull_kernel).  They read the launch descriptor sd,
+// the first argument, and nothing else: one batch of scalar loads at the wave's
+// start.  The other instances read the arguments after it and never sd.
 template <int MODE, bool SAT, bool FUSED>
 __global__ void __launch_bounds__(GGS_DEPTH_SPLIT ? 2 * NT : NT, OCC)
-raster_kernel(const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, int B, int N, int H, int W, int nTX,
-              int nTiles,
+raster_kernel(const StripLaunch sd, const SplatRec* __restrict__ recs, const int4* __restrict__ bnds, int B, int N,
+              int H, int W, int nTX, int nTiles,
               float bg_r, float bg_g, float bg_b, float* __restrict__ img,
               const float4* __restrict__ plan, float* __restrict__ partials,
               const int* __restrict__ tile_order, const unsigned char* __restrict__ dirty,
-              const float* __restrict__ clean, const int* __restrict__ live, int CH, FinFused fin, int simds,
-              const int* __restrict__ swords, const uint64_t* __restrict__ smasks) {
-    // the instances with visit words compact prep's strip words (launch_raster hands
-    // batches without them to bounds_cull_kernel)
+              const float* __restrict__ clean, const int* __restrict__ live, int CH, FinFused fin, int simds) {
     constexpr bool PRE = !SAT && !FUSED && !GGS_DEPTH_SPLIT;
-    raster_body<MODE, SAT, FUSED, false, false, PRE>(recs, bnds, B, N, H, W, nTX, nTiles, bg_r, bg_g, bg_b, img, plan,
-                                                     partials, tile_order, dirty, clean, live, CH, fin, simds, 1,
-                                                     nullptr, swords, smasks);
+    if constexpr (PRE)
+        raster_body<MODE, false, false, false, false, true>(sd.recs, nullptr, 0, sd.N, sd.H, sd.W, 0, 0, sd.bg_r,
+                                                            sd.bg_g, sd.bg_b, sd.img, sd.plan, sd.partials, nullptr,
+                                                            nullptr, nullptr, nullptr, 0, FinFused{}, 0, 1, nullptr,
+                                                            sd.words, sd.masks, &sd);
+    else
+        raster_body<MODE, SAT, FUSED, false>(recs, bnds, B, N, H, W, nTX, nTiles, bg_r, bg_g, bg_b, img, plan,
+                                             partials, tile_order, dirty, clean, live, CH, fin, simds, 1);
 }
 
 // raster_kernel<MODE, false, false> with the cull of its own from the bounds, for
@@ -1462,14 +1500,43 @@ hipError_t launch_raster(hipStream_t st, int mode, const SplatRec* recs, const i
     const FinFused ff = (mode != 0 && fin) ? *fin : FinFused{};
     if (GGS_DEPTH_SPLIT) simds = 0;
     // strip words written by the launch's prep (launch_prep): whole batches only
-    const bool strips = !GGS_DEPTH_SPLIT && sw.masks && sw.words && !live && !dirty && strip_words_ok(N);
-    const int* const swords = strips ? sw.words : nullptr;
-    const uint64_t* const smasks = strips ? sw.masks : nullptr;
+    // ... and a grid whose decode the host can prepare (StripLaunch; else the twin, which divides)
+    StripLaunch sd;
+    const bool strips = !GGS_DEPTH_SPLIT && sw.masks && sw.words && sw.table && !live && !dirty && strip_words_ok(N) &&
+                        nTX * kStripsPerTile <= 0x10000 && nTiles / nTX <= 0x8000 &&
+                        strip_launch_grid(B, nTiles, CH, simds, &sd);
+    if (strips) {
+        const int nTY = nTiles / nTX;
+        sd.table = sw.table;
+        sd.masks = sw.masks;
+        sd.words = sw.words;
+        sd.N = N;
+        sd.ncols = nTX * kStripsPerTile;
+        sd.ncp = strip_mask_chunks(N);
+        sd.words_b = nTY * N;
+        sd.masks_b = (2 * sd.ncols + nTY) * sd.ncp;
+        sd.nslots = nTiles * kStripsPerTile;
+        sd.recs = recs;
+        sd.plan = plan;
+        sd.partials = partials;
+        sd.img = img;
+        sd.H = H;
+        sd.W = W;
+        sd.bg_r = bg[0];
+        sd.bg_g = bg[1];
+        sd.bg_b = bg[2];
+    }
     // FUSED is a template parameter, so the instances without the fold carry none
     // of its code (a runtime test left the SA raster 1 % slower than round 3's)
 #define GGS_RASTER(M, S, F)                                                                    \
-    hipLaunchKernelGGL((raster_kernel<M, S, F>), grid, (M) ? block_f : block, 0, st, recs, bnds, B, N, H, W, nTX, nTiles, \
-                       bg[0], bg[1], bg[2], img, plan, partials, tile_order, dirty, clean, live, CH, ff, simds, swords, smasks)
+    hipLaunchKernelGGL((raster_kernel<M, S, F>), grid, (M) ? block_f : block, 0, st, StripLaunch{}, recs, bnds, B, N, H, \
+                       W, nTX, nTiles, bg[0], bg[1], bg[2], img, plan, partials, tile_order, dirty, clean, live, CH, ff, \
+                       simds)
+    // the strip-words instances take the launch descriptor alone
+#define GGS_RASTER_PRE(M)                                                                      \
+    hipLaunchKernelGGL((raster_kernel<M, false, false>), grid, (M) ? block_f : block, 0, st, sd, nullptr, nullptr, 0, \
+                       0, 0, 0, 0, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, \
+                       FinFused{}, 0)
     // the saturation check only where strip lists can grow long (N > SAT_MIN_SPLATS);
     // at the bench's 256 splats the kernel without it is the faster code (+1.6 %)
 #define GGS_RASTER_MULTI(S, F)                                                                 \
@@ -1485,13 +1552,14 @@ hipError_t launch_raster(hipStream_t st, int mode, const SplatRec* recs, const i
         else { if (!sat) GGS_RASTER_MULTI(false, true); else GGS_RASTER_MULTI(true, true); }
     }
     else if (mode == 0) {                                                                         // image
-        if (sat) GGS_RASTER(0, true, false); else if (strips) GGS_RASTER(0, false, false); else GGS_BOUNDS_CULL(0);
+        if (sat) GGS_RASTER(0, true, false); else if (strips) GGS_RASTER_PRE(0); else GGS_BOUNDS_CULL(0);
     } else if (!ff.ctr) {                                                                         // fitness
-        if (sat) GGS_RASTER(1, true, false); else if (strips) GGS_RASTER(1, false, false); else GGS_BOUNDS_CULL(1);
+        if (sat) GGS_RASTER(1, true, false); else if (strips) GGS_RASTER_PRE(1); else GGS_BOUNDS_CULL(1);
     }
     else { if (!sat) GGS_RASTER(1, false, true); else GGS_RASTER(1, true, true); }  // + folded finalize
 #undef GGS_BOUNDS_CULL
 #undef GGS_RASTER_MULTI
+#undef GGS_RASTER_PRE
 #undef GGS_RASTER
     return hipGetLastError();
 }

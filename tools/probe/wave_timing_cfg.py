@@ -55,7 +55,8 @@ t0 = rt0.min()
 s_us, e_us = (rt0 - t0) / 100.0, (rt1 - t0) / 100.0
 dur = e_us - s_us
 visits = buf[:, 6].astype(np.int64)
-ts = np.linspace(0, e_us.max(), 400)
+entry = (buf[:, 5] >> np.uint64(40)).astype(np.float64)
+ts =np.linspace(0, e_us.max(), 400)
 live = np.array([((s_us <= t) & (e_us > t)).sum() for t in ts])
 dt = ts[1] - ts[0]
 xcc = (buf[:, 5] >> np.uint64(32)).astype(np.int64) & 0xF
@@ -69,6 +70,11 @@ res = {"H": H, "splats": a.splats, "batch": a.batch, "waves": n_waves, "span_us"
        "mean_live": float(live.mean()),
        "phase_frac": {k: round(float(buf[:, i].astype(np.float64).sum() / buf[:, 2:5].astype(np.float64).sum()), 3)
                       for k, i in (("cull", 2), ("visits", 3), ("epilogue", 4))},
+       # the cull's clocks before the strip-words cull issues its first load (record 5, bits 40-63)
+       "cull_entry_frac": round(float(entry.sum() / buf[:, 2:5].astype(np.float64).sum()), 4),
+       "cull_entry_of_cull": round(float(entry.sum() / max(buf[:, 2].astype(np.float64).sum(), 1.0)), 4),
+       "cull_entry_clk_p50": float(np.median(entry)), "cull_clk_p50": float(np.median(buf[:, 2].astype(np.float64))),
+       "epilogue_clk_p50": float(np.median(buf[:, 4].astype(np.float64))),
        "blended": {k: int(np.percentile(buf[:, 7].astype(np.int64), q)) for k, q in (("p50", 50), ("max", 100))},
        "clk_per_blended_visit_p50": float(np.median(buf[:, 3].astype(np.float64) /
                                                     np.maximum(buf[:, 7].astype(np.float64), 1))),
