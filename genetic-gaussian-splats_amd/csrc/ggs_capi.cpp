@@ -140,6 +140,7 @@ struct Workspace {
     DevBuf maskws;                    // target preparation / importance mask scratch (ggs_mask.hip)
     DevBuf swords, smasks;            // strip words and masks, prep -> raster (StripWords)
     DevBuf gf9, gi4, gpart, gout;     // fitness gradient: prep's stage outputs, strip partials, unwanted fitness
+    DevBuf lpart, limg, lcot;         // image loss: tile partials; ggs_loss_grad's image and cotangent
     int order_H = -1, order_W = -1;   // (H, W) the tile order was built for
     bool strips_ok = false;           // ... and whether its strip table holds that canvas
     uint64_t plan_key = 0;            // inputs the plan was built from (0: none / volatile)
@@ -189,6 +190,7 @@ struct DevCtx {
     DevBuf gen, out, target, mask, ggrad;   // ggrad: ggs_fitness_grad's [B,N,9]
     DevBuf set_plan, set_wpart;            // ggs_fitness_grad_targets' own plan set
     DevBuf prep_in, prep_tgt, prep_mask;   // ggs_targets_prepare / ggs_quantiles staging
+    DevBuf loss_img, loss_cot, loss_out;   // ggs_image_loss / ggs_loss_grad staging
     PinBuf h_out;                  // the fitness scalars (render and genomes go straight to / from the caller)
     uint64_t target_key = 0, mask_key = 0;
     size_t target_bytes = 0, mask_bytes = 0;
@@ -618,6 +620,65 @@ int run_render_vjp(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int
     return GGS_OK;
 }
 
+// ---- image losses ----------------------------------------------------
+int check_loss_params(const ggs_loss_params* p) {
+    if (!p) return fail(GGS_EINVAL, "null ggs_loss_params");
+    const float w[3] = {p->w_l1, p->w_mse, p->w_ssim};
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(w[i]) || w[i] < 0.0f)
+            return fail(GGS_EINVAL, "loss weights (%g, %g, %g) must be finite and >= 0", w[0], w[1], w[2]);
+    if (w[0] == 0.0f && w[1] == 0.0f && w[2] == 0.0f) return fail(GGS_EINVAL, "loss weights are all zero");
+    return GGS_OK;
+}
+
+// ggs_image_loss*'s shape rules: the group rule of ggs_fitness_device_planset and a grid
+// of B * tiles workgroups below 2^31.
+int check_loss_dims(int64_t B, int32_t K, int32_t group, int32_t H, int32_t W) {
+    if (B < 1) return fail(GGS_EINVAL, "B=%lld must be >= 1", (long long)B);
+    if (H < 1 || W < 1) return fail(GGS_EINVAL, "H=%d, W=%d must be >= 1", H, W);
+    if (group < 1) return fail(GGS_EINVAL, "group=%d must be >= 1", group);
+    if (K < 1) return fail(GGS_EINVAL, "K=%d images: must be >= 1", K);
+    if (B % group != 0) return fail(GGS_EINVAL, "B=%lld is not a multiple of group=%d", (long long)B, group);
+    if (B / group > K)
+        return fail(GGS_EINVAL, "B / group = %lld images wanted, the set holds %d", (long long)(B / group), K);
+    if (B >= (int64_t)1 << 31 || B * image_loss_tiles(H, W) >= (int64_t)1 << 31)
+        return fail(GGS_EINVAL, "B*tiles = %lld exceeds the grid limit; split the batch",
+                    (long long)(B * image_loss_tiles(H, W)));
+    return GGS_OK;
+}
+
+// loss [B] and, unless d_cot is null, the cotangent [B][H][W][3]; the tile partials are
+// the stream's workspace.
+int run_image_loss(DevCtx* c, hipStream_t st, const float* d_img, int64_t B, const float* d_targets, int group, int H,
+                   int W, const ggs_loss_params& p, float* d_loss, float* d_cot) {
+    Workspace* w = workspace_for(c, st);
+    int rc;
+    if ((rc = ensure(w->lpart, image_loss_partial_bytes(B, H, W), st))) return rc;
+    const float wt[3] = {p.w_l1, p.w_mse, p.w_ssim};
+    GGS_HIP(launch_image_loss(st, d_img, B, d_targets, group, H, W, wt, w->lpart.p, d_loss, d_cot));
+    return GGS_OK;
+}
+
+// ggs_loss_grad*'s argument errors: the VJP's, the loss's, the weights'.
+int check_loss_grad(int64_t B, int32_t N, int32_t C, int32_t layout, int32_t K, int32_t group, int32_t H, int32_t W,
+                    const ggs_loss_params* p) {
+    int rc = check_vjp_dims(B, N, C, layout, H, W);
+    if (rc == GGS_OK) rc = check_loss_dims(B, K, group, H, W);
+    if (rc == GGS_OK) rc = check_loss_params(p);
+    return rc;
+}
+
+// render -> image loss -> VJP, the three stages as their own entry points issue them;
+// d_img / d_cot [B][H][W][3] are the caller's scratch.
+int run_loss_grad(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C, int layout,
+                  const float* d_targets, int group, int H, int W, float k, const float bg[3],
+                  const ggs_loss_params& p, float* d_loss, float* d_grad, float* d_img, float* d_cot) {
+    int rc;
+    if ((rc = run_render(c, st, d_gen, B, N, C, H, W, k, bg, d_img, layout == GGS_LAYOUT_AXES))) return rc;
+    if ((rc = run_image_loss(c, st, d_img, B, d_targets, group, H, W, p, d_loss, d_cot))) return rc;
+    return run_render_vjp(c, st, d_gen, B, N, C, layout, H, W, k, bg, d_cot, d_grad);
+}
+
 // Fitness (the existing prep -> raster -> finalize path, so ggs_fitness_device's
 // bits) and its gradient [B][N][9].  d_out may be null.
 int run_fitness_grad(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C, const float* d_target,
@@ -756,11 +817,12 @@ void ggs_shutdown(void) {
         for (auto& w : c->ws) {
             if (w->stream) (void)hipStreamSynchronize(w->stream);
             for (DevBuf* b : {&w->recs, &w->bnds, &w->partials, &w->wpartials, &w->order, &w->plan, &w->fctr, &w->maskws,
-                              &w->swords, &w->smasks, &w->gf9, &w->gi4, &w->gpart, &w->gout})
+                              &w->swords, &w->smasks, &w->gf9, &w->gi4, &w->gpart, &w->gout,
+                              &w->lpart, &w->limg, &w->lcot})
                 if (b->p) (void)hipFree(b->p);
         }
         for (DevBuf* b : {&c->gen, &c->out, &c->target, &c->mask, &c->ggrad, &c->set_plan, &c->set_wpart, &c->prep_in,
-                          &c->prep_tgt, &c->prep_mask})
+                          &c->prep_tgt, &c->prep_mask, &c->loss_img, &c->loss_cot, &c->loss_out})
             if (b->p) (void)hipFree(b->p);
         for (PinBuf* b : {&c->h_out})
             if (b->p) (void)hipHostFree(b->p);
@@ -1113,6 +1175,42 @@ int ggs_render_vjp_device(int32_t device, void* stream, const float* d_genomes, 
                           d_cot_bhw3, d_grad_BN9);
 }
 
+int ggs_image_loss_device(int32_t device, void* stream, const float* d_img_bhw3, int64_t B,
+                          const float* d_targets_khw3, int32_t K, int32_t group, int32_t H, int32_t W,
+                          const ggs_loss_params* p, float* d_loss_B, float* d_cot_bhw3) {
+    int rc = check_loss_dims(B, K, group, H, W);
+    if (rc) return rc;
+    if ((rc = check_loss_params(p))) return rc;
+    if (!d_img_bhw3 || !d_targets_khw3 || !d_loss_B) return fail(GGS_EINVAL, "null image/targets/loss");
+    DevCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    return run_image_loss(c, (hipStream_t)stream, d_img_bhw3, B, d_targets_khw3, group, H, W, *p, d_loss_B,
+                          d_cot_bhw3);
+}
+
+int ggs_loss_grad_device(int32_t device, void* stream, const float* d_genomes, int64_t B, int32_t N, int32_t C,
+                         int32_t layout, const float* d_targets_khw3, int32_t K, int32_t group, int32_t H, int32_t W,
+                         float k_sigma, const float* bg, const ggs_loss_params* p, float* d_loss_B,
+                         float* d_grad_BN9) {
+    int rc = check_loss_grad(B, N, C, layout, K, group, H, W, p);
+    if (rc) return rc;
+    if (!d_genomes || !d_targets_khw3 || !d_loss_B || !d_grad_BN9)
+        return fail(GGS_EINVAL, "null genomes/targets/loss/grad");
+    DevCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    const float bg1[3] = {1.f, 1.f, 1.f};
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    hipStream_t st = (hipStream_t)stream;
+    Workspace* w = workspace_for(c, st);
+    const size_t vbytes = sizeof(float) * 3 * (size_t)H * W * (size_t)B;
+    if ((rc = ensure(w->limg, vbytes, st)) || (rc = ensure(w->lcot, vbytes, st))) return rc;
+    return run_loss_grad(c, st, d_genomes, B, N, C, layout, d_targets_khw3, group, H, W, k_sigma, bg ? bg : bg1, *p,
+                         d_loss_B, d_grad_BN9, (float*)w->limg.p, (float*)w->lcot.p);
+}
+
 }  // extern "C"
 
 namespace ggs {
@@ -1356,6 +1454,74 @@ int ggs_render_vjp(const float* genomes, int64_t B, int32_t N, int32_t C, int32_
     if ((rc = run_render_vjp(c, st, (const float*)c->gen.p, B, N, C, layout, H, W, k_sigma, bg ? bg : bg1,
                              (const float*)c->out.p, (float*)c->ggrad.p)))
         return rc;
+    GGS_HIP(hipMemcpyAsync(grad_BN9, c->ggrad.p, dbytes, hipMemcpyDeviceToHost, st));
+    return drain.drain();
+}
+
+int ggs_image_loss(const float* img_bhw3, int64_t B, const float* targets_khw3, int32_t K, int32_t group, int32_t H,
+                   int32_t W, const ggs_loss_params* p, float* loss_B, float* cot_bhw3, int32_t device) {
+    int rc = check_loss_dims(B, K, group, H, W);
+    if (rc) return rc;
+    if ((rc = check_loss_params(p))) return rc;
+    if (!img_bhw3 || !targets_khw3 || !loss_B) return fail(GGS_EINVAL, "null image/targets/loss");
+    DevCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    const size_t plane = sizeof(float) * 3 * (size_t)H * W;
+    const size_t vbytes = plane * (size_t)B, tbytes = plane * (size_t)K;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    hipStream_t st = c->stream;
+    StreamDrain drain;                  // after the context lock: drained on every return
+    if ((rc = ensure(c->loss_img, vbytes, st)) || (cot_bhw3 && (rc = ensure(c->loss_cot, vbytes, st))) ||
+        (rc = ensure(c->loss_out, sizeof(float) * (size_t)B, st)) || (rc = ensure(c->target, tbytes, st)))
+        return rc;
+    GGS_HIP(hipStreamSynchronize(st));  // the previous call's work is done with the staging
+    drain.add(c->dev, st);
+    // the staging no longer holds what the single-target calls' content keys describe
+    c->target_key = 0;
+    c->target_bytes = 0;
+    GGS_HIP(hipMemcpyAsync(c->loss_img.p, img_bhw3, vbytes, hipMemcpyHostToDevice, st));
+    GGS_HIP(hipMemcpyAsync(c->target.p, targets_khw3, tbytes, hipMemcpyHostToDevice, st));
+    float* d_cot = cot_bhw3 ? (float*)c->loss_cot.p : nullptr;
+    if ((rc = run_image_loss(c, st, (const float*)c->loss_img.p, B, (const float*)c->target.p, group, H, W, *p,
+                             (float*)c->loss_out.p, d_cot)))
+        return rc;
+    GGS_HIP(hipMemcpyAsync(loss_B, c->loss_out.p, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st));
+    if (cot_bhw3) GGS_HIP(hipMemcpyAsync(cot_bhw3, d_cot, vbytes, hipMemcpyDeviceToHost, st));
+    return drain.drain();
+}
+
+int ggs_loss_grad(const float* genomes, int64_t B, int32_t N, int32_t C, int32_t layout, const float* targets_khw3,
+                  int32_t K, int32_t group, int32_t H, int32_t W, float k_sigma, const float* bg,
+                  const ggs_loss_params* p, float* loss_B, float* grad_BN9, int32_t device) {
+    int rc = check_loss_grad(B, N, C, layout, K, group, H, W, p);
+    if (rc) return rc;
+    if (!genomes || !targets_khw3 || !loss_B || !grad_BN9) return fail(GGS_EINVAL, "null genomes/targets/loss/grad");
+    DevCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    const float bg1[3] = {1.f, 1.f, 1.f};
+    const size_t plane = sizeof(float) * 3 * (size_t)H * W;
+    const size_t vbytes = plane * (size_t)B, tbytes = plane * (size_t)K;
+    const size_t gbytes = sizeof(float) * (size_t)N * C * (size_t)B, dbytes = sizeof(float) * 9 * (size_t)N * (size_t)B;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    hipStream_t st = c->stream;
+    StreamDrain drain;                  // after the context lock: drained on every return
+    if ((rc = ensure(c->loss_img, vbytes, st)) || (rc = ensure(c->loss_cot, vbytes, st)) ||
+        (rc = ensure(c->loss_out, sizeof(float) * (size_t)B, st)) || (rc = ensure(c->target, tbytes, st)) ||
+        (rc = ensure(c->gen, gbytes, st)) || (rc = ensure(c->ggrad, dbytes, st)))
+        return rc;
+    GGS_HIP(hipStreamSynchronize(st));  // the previous call's work is done with the staging
+    drain.add(c->dev, st);
+    c->target_key = 0;
+    c->target_bytes = 0;
+    GGS_HIP(hipMemcpyAsync(c->gen.p, genomes, gbytes, hipMemcpyHostToDevice, st));
+    GGS_HIP(hipMemcpyAsync(c->target.p, targets_khw3, tbytes, hipMemcpyHostToDevice, st));
+    if ((rc = run_loss_grad(c, st, (const float*)c->gen.p, B, N, C, layout, (const float*)c->target.p, group, H, W,
+                            k_sigma, bg ? bg : bg1, *p, (float*)c->loss_out.p, (float*)c->ggrad.p,
+                            (float*)c->loss_img.p, (float*)c->loss_cot.p)))
+        return rc;
+    GGS_HIP(hipMemcpyAsync(loss_B, c->loss_out.p, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st));
     GGS_HIP(hipMemcpyAsync(grad_BN9, c->ggrad.p, dbytes, hipMemcpyDeviceToHost, st));
     return drain.drain();
 }
@@ -2047,7 +2213,8 @@ void release_workspace(DevCtx* c, hipStream_t st) {
         if ((*it)->stream == st) {
             Workspace* w = it->get();
             for (DevBuf* b : {&w->recs, &w->bnds, &w->partials, &w->wpartials, &w->order, &w->plan, &w->fctr,
-                              &w->maskws, &w->swords, &w->smasks, &w->gf9, &w->gi4, &w->gpart, &w->gout})
+                              &w->maskws, &w->swords, &w->smasks, &w->gf9, &w->gi4, &w->gpart, &w->gout,
+                              &w->lpart, &w->limg, &w->lcot})
                 if (b->p) (void)hipFree(b->p);
             c->ws.erase(it);
             return;
@@ -3572,13 +3739,19 @@ struct RefineSession {
     // set of K made at create; candidate b against image b / group (0: the one target)
     int K = 1, group = 0;
     DevBuf plan, wpart;
+    // ggs_refine_create_loss: fits is the image loss of the render against image b / group
+    // (no plan, no mask); the render and its cotangent live in img / cot [B][H][W][3]
+    bool use_loss = false;
+    ggs_loss_params loss{};
+    float bg[3] = {1.f, 1.f, 1.f};
+    DevBuf img, cot;
 };
 
 std::atomic<uint64_t> g_refine_serial{1};
 
 void refine_free(RefineSession* s) {
     for (DevBuf* b : {&s->x, &s->m, &s->v, &s->grad, &s->fits, &s->best_x, &s->best_fit, &s->target, &s->mask,
-                      &s->plan, &s->wpart})
+                      &s->plan, &s->wpart, &s->img, &s->cot})
         if (b->p) (void)hipFree(b->p);
     if (s->st) {
         release_workspace(s->c, s->st);
@@ -3590,6 +3763,17 @@ void refine_free(RefineSession* s) {
 int refine_eval(RefineSession* s, bool grad) {
     const ggs_ga_config& c = s->cfg;
     const float* d_mask = s->mask.p ? (const float*)s->mask.p : nullptr;
+    if (s->use_loss) {
+        if (grad)
+            return run_loss_grad(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, GGS_LAYOUT_AXES,
+                                 (const float*)s->target.p, s->group, c.H, c.W, c.k_sigma, s->bg, s->loss,
+                                 (float*)s->fits.p, (float*)s->grad.p, (float*)s->img.p, (float*)s->cot.p);
+        int rc = run_render(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, c.H, c.W, c.k_sigma, s->bg,
+                            (float*)s->img.p, true);
+        if (rc) return rc;
+        return run_image_loss(s->c, s->st, (const float*)s->img.p, s->B, (const float*)s->target.p, s->group, c.H, c.W,
+                              s->loss, (float*)s->fits.p, nullptr);
+    }
     if (s->group > 0) {
         if (grad)
             return run_fitness_grad_planned(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, (const float4*)s->plan.p,
@@ -3608,16 +3792,19 @@ int refine_eval(RefineSession* s, bool grad) {
                        c.fitness_mode, c.boost_beta, c.H, c.W, c.k_sigma, (float*)s->fits.p, s->plan_key);
 }
 
-// ggs_refine_create (group 0: one target and mask) and ggs_refine_create_targets
-// (group >= 1: targets [K][H][W][3], masks [K][H][W], one plan set)
+// ggs_refine_create (group 0: one target and mask), ggs_refine_create_targets
+// (group >= 1: targets [K][H][W][3], masks [K][H][W], one plan set) and
+// ggs_refine_create_loss (loss set: group >= 1, targets [K][H][W][3], no mask and no plan)
 int refine_create(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p, const float* target,
-                  const float* mask, int32_t K, const float* genomes_BN9, int32_t B, int32_t group, void** handle) {
+                  const float* mask, int32_t K, const float* genomes_BN9, int32_t B, int32_t group, void** handle,
+                  const ggs_loss_params* loss = nullptr, const float* bg = nullptr) {
     if (!cfg || !p || !target || !genomes_BN9 || !handle) return fail(GGS_EINVAL, "null argument");
     const ggs_ga_config& c = *cfg;
-    int rc = group == 0 ? check_grad_dims(B, c.n_splats, 9, c.H, c.W, c.fitness_mode, mask)
-                        : check_grad_set(B, c.n_splats, 9, c.H, c.W, c.fitness_mode, mask, K, group);
+    int rc = loss ? check_loss_grad(B, c.n_splats, 9, GGS_LAYOUT_AXES, K, group, c.H, c.W, loss)
+             : group == 0 ? check_grad_dims(B, c.n_splats, 9, c.H, c.W, c.fitness_mode, mask)
+                          : check_grad_set(B, c.n_splats, 9, c.H, c.W, c.fitness_mode, mask, K, group);
     if (rc) return rc;
-    if (group > 0 && (rc = check_dims(K, 1, 9, c.H, c.W))) return rc;
+    if (!loss && group > 0 && (rc = check_dims(K, 1, 9, c.H, c.W))) return rc;
     if ((rc = refine_check_params(p))) return rc;
     DevCtx* ctx = nullptr;
     if ((rc = get_ctx(device, &ctx))) return rc;
@@ -3630,6 +3817,12 @@ int refine_create(int32_t device, const ggs_ga_config* cfg, const ggs_refine_par
     s->N = c.n_splats;
     s->K = K;
     s->group = group;
+    if (loss) {
+        s->use_loss = true;
+        s->loss = *loss;
+        if (bg) memcpy(s->bg, bg, sizeof s->bg);
+    }
+    const bool planned = group > 0 && !loss;
     s->plan_key = (1ull << 63) | g_refine_serial.fetch_add(1);     // host_plan_key never sets bit 63
     const size_t pb = sizeof(float) * 9 * (size_t)B * s->N, hw = (size_t)K * c.H * c.W;
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -3643,8 +3836,10 @@ int refine_create(int32_t device, const ggs_ga_config* cfg, const ggs_refine_par
         (rc = ensure(s->best_fit, sizeof(double) * (size_t)B, s->st)) ||
         (rc = ensure(s->target, sizeof(float) * 3 * hw, s->st)) ||
         (mask && (rc = ensure(s->mask, sizeof(float) * hw, s->st))) ||
-        (group > 0 && ((rc = ensure(s->plan, (size_t)K * plan_bytes(c.H, c.W), s->st)) ||
-                       (rc = ensure(s->wpart, (size_t)K * plan_wsum_bytes(c.H, c.W), s->st)))))
+        (planned && ((rc = ensure(s->plan, (size_t)K * plan_bytes(c.H, c.W), s->st)) ||
+                     (rc = ensure(s->wpart, (size_t)K * plan_wsum_bytes(c.H, c.W), s->st)))) ||
+        (loss && ((rc = ensure(s->img, sizeof(float) * 3 * (size_t)B * c.H * c.W, s->st)) ||
+                  (rc = ensure(s->cot, sizeof(float) * 3 * (size_t)B * c.H * c.W, s->st)))))
         return bail(rc);
     std::vector<double> inf((size_t)B, (double)INFINITY);
     if (hipMemcpyAsync(s->target.p, target, sizeof(float) * 3 * hw, hipMemcpyHostToDevice, s->st) ||
@@ -3655,7 +3850,7 @@ int refine_create(int32_t device, const ggs_ga_config* cfg, const ggs_refine_par
         hipMemsetAsync(s->m.p, 0, pb, s->st) || hipMemsetAsync(s->v.p, 0, pb, s->st) ||
         hipMemsetAsync(s->grad.p, 0, pb, s->st))
         return bail(fail(GGS_EHIP, "upload failed"));
-    if (group > 0 &&
+    if (planned &&
         launch_plan_set(s->st, (const float*)s->target.p, mask ? (const float*)s->mask.p : nullptr, c.fitness_mode,
                         c.boost_beta, c.H, c.W, K, (float4*)s->plan.p, (float*)s->wpart.p) != hipSuccess)
         return bail(fail(GGS_EHIP, "plan launch failed"));
@@ -3678,6 +3873,13 @@ int ggs_refine_create_targets(int32_t device, const ggs_ga_config* cfg, const gg
                               int32_t B, int32_t group, void** handle) {
     if (group < 1) return fail(GGS_EINVAL, "group=%d must be >= 1", group);
     return ggs::refine_create(device, cfg, p, targets_khw3, masks_khw, K, genomes_BN9, B, group, handle);
+}
+
+int ggs_refine_create_loss(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p,
+                           const ggs_loss_params* loss, const float* bg, const float* targets_khw3, int32_t K,
+                           const float* genomes_BN9, int32_t B, int32_t group, void** handle) {
+    if (!loss) return fail(GGS_EINVAL, "null ggs_loss_params");
+    return ggs::refine_create(device, cfg, p, targets_khw3, nullptr, K, genomes_BN9, B, group, handle, loss, bg);
 }
 
 int ggs_refine_run(void* handle, int32_t n_steps) {

@@ -581,6 +581,16 @@ hipError_t launch_refine_best(hipStream_t st, const float* x, const float* fits,
 hipError_t launch_refine_adam(hipStream_t st, float* x, float* m, float* v, const float* g, int B, int N,
                               const RefineStepDev& p);
 
+// ---- image losses (ggs_loss.hip) ---------------------------------------
+// loss [B] = w[0] mean|x - y| + w[1] mean (x - y)^2 + w[2] (1 - mean SSIM) of img
+// [B][H][W][3] against targets [K][H][W][3] (candidate b against image b / group) and,
+// unless cot is null, cot [B][H][W][3] = d loss / d img.  partials:
+// image_loss_partial_bytes of scratch.  B * image_loss_tiles must stay below 2^31.
+int64_t image_loss_tiles(int H, int W);
+size_t image_loss_partial_bytes(int64_t B, int H, int W);
+hipError_t launch_image_loss(hipStream_t st, const float* img, int64_t B, const float* targets, int group, int H, int W,
+                             const float w[3], void* partials, float* loss, float* cot);
+
 // ---- RCCL (ggs_comm.cpp) ----------------------------------------------------
 // Grouped in-place all-gather over single-process communicators (ggs_comm_init_local):
 // buf[d] holds shard d at buf[d] + d*per; afterwards every buf[d] holds all n shards.

@@ -64,6 +64,11 @@ class RefineParams(C.Structure):
     _fields_ = [("lr", C.c_float * 9), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float)]
 
 
+class LossParamsC(C.Structure):
+    """ggs_loss_params (include/ggs.h)."""
+    _fields_ = [("w_l1", C.c_float), ("w_mse", C.c_float), ("w_ssim", C.c_float)]
+
+
 class GaPolish(C.Structure):
     """ggs_ga_polish (include/ggs.h)."""
     _fields_ = [("every", C.c_int32), ("n_steps", C.c_int32), ("n_rows", C.c_int32), ("adam", RefineParams)]
@@ -188,6 +193,20 @@ SIGNATURES = {
                                            _f32p, _f32p]),
     "ggs_refine_create_targets": (C.c_int, [C.c_int32, C.POINTER(GaConfig), C.POINTER(RefineParams), _f32p, _f32p,
                                             C.c_int32, _f32p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "ggs_image_loss_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_int32, C.POINTER(LossParamsC), C.c_void_p,
+                                        C.c_void_p]),
+    "ggs_image_loss": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                 C.POINTER(LossParamsC), _f32p, _f32p, C.c_int32]),
+    "ggs_loss_grad_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_float, _f32p, C.POINTER(LossParamsC), C.c_void_p, C.c_void_p]),
+    "ggs_loss_grad": (C.c_int, [_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _f32p, C.c_int32, C.c_int32,
+                                C.c_int32, C.c_int32, C.c_float, _f32p, C.POINTER(LossParamsC), _f32p, _f32p,
+                                C.c_int32]),
+    "ggs_refine_create_loss": (C.c_int, [C.c_int32, C.POINTER(GaConfig), C.POINTER(RefineParams),
+                                         C.POINTER(LossParamsC), _f32p, _f32p, C.c_int32, _f32p, C.c_int32,
+                                         C.c_int32, C.POINTER(C.c_void_p)]),
     "ggs_ga_islands_set_polish": (C.c_int, [C.c_void_p, C.POINTER(GaPolish)]),
     "ggs_refine_run": (C.c_int, [C.c_void_p, C.c_int32]),
     "ggs_refine_read": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p]),

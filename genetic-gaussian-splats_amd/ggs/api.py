@@ -10,7 +10,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -240,6 +240,78 @@ def render_vjp(genomes, cot, H: int, W: int, *, k_sigma: float = 3.0, background
     return grad
 
 
+class LossParams(NamedTuple):
+    """Weights of the image loss ``l1 * mean|x - y| + mse * mean (x - y)^2 + ssim * (1 - mean
+    SSIM(x, y))``; the default is the 3DGS / GaussianImage loss, lambda 0.2."""
+    l1: float = 0.8
+    mse: float = 0.0
+    ssim: float = 0.2
+
+
+def loss_params_c(params) -> "_lib.LossParamsC":
+    """ggs_loss_params of a ``LossParams`` (or any three weights l1, mse, ssim; None: the default)."""
+    p = LossParams() if params is None else LossParams(*params)
+    return _lib.LossParamsC(float(p.l1), float(p.mse), float(p.ssim))
+
+
+def _targets4d(targets, B: int, H: int, W: int, group: Optional[int]):
+    """[K,H,W,3] float32 targets ([H,W,3]: one image for every candidate) and the group."""
+    tgt = as_f32(targets)
+    if tgt.ndim == 3:
+        if group is not None:
+            raise GGSInputError("group= needs 4-D targets [K,H,W,3]")
+        tgt, group = tgt[None], B
+    K = tgt.shape[0]
+    if tgt.ndim != 4 or tgt.shape != (K, H, W, 3):
+        raise GGSInputError(f"targets must be [K,H,W,3] or [H,W,3] with (H, W) = {(H, W)}, got {tuple(tgt.shape)}")
+    if group is None:
+        group = max(B // max(K, 1), 1)
+    return tgt, K, int(group)
+
+
+def image_loss(img, targets, params=None, *, group: Optional[int] = None, cot: bool = True, device=None):
+    """The image loss of ``img`` [B,H,W,3] ([H,W,3]: one image) against ``targets`` [K,H,W,3]
+    (image b against target ``b // group``, ``group`` defaults to B // K) or [H,W,3] (one
+    target for all) → (loss float32 [B], cot float32 [B,H,W,3] = d loss / d img), or the loss
+    alone with ``cot=False`` (the same bits).  DESIGN.md §8f has the definition; float64
+    between the float32 inputs and outputs.  One device."""
+    x = as_f32(img)
+    if x.ndim == 3:
+        x = x[None]
+    if x.ndim != 4 or x.shape[3] != 3:
+        raise GGSInputError(f"img must be [B,H,W,3] or [H,W,3], got {tuple(x.shape)}")
+    B, H, W, _ = x.shape
+    tgt, K, group = _targets4d(targets, B, H, W, group)
+    prm = loss_params_c(params)
+    loss = np.empty((B,), np.float32)
+    v = np.empty((B, H, W, 3), np.float32) if cot else None
+    # arguments are validated before the library looks for a device
+    check(lib.ggs_image_loss(_fp(x), B, _fp(tgt), K, group, H, W, C.byref(prm), _fp(loss),
+                             None if v is None else _fp(v), device_index(device)), "ggs_image_loss")
+    return (loss, v) if cot else loss
+
+
+def loss_grad(genomes, targets, H: int, W: int, params=None, *, k_sigma: float = 3.0,
+              background=(1.0, 1.0, 1.0), layout="axes", group: Optional[int] = None, device=None):
+    """The image loss of the render of ``genomes`` [B,N,C] ([N,C]) and its gradient with
+    respect to the nine genes of every splat → (loss float32 [B], grad float32 [B,N,9]):
+    ``render`` → ``image_loss`` → ``render_vjp`` in one call, with their bits.  ``targets``
+    and ``group`` as ``image_loss``; ``layout`` as ``render_vjp`` (default: axes-angle
+    genomes, what the optimisers keep).  One device."""
+    g = _genomes3d(genomes, "loss_grad")
+    B, N, Cc = g.shape
+    H, W = int(H), int(W)
+    lay = layout_id(layout)
+    tgt, K, group = _targets4d(targets, B, H, W, group)
+    prm = loss_params_c(params)
+    bg = _background3(background)
+    loss = np.empty((B,), np.float32)
+    grad = np.empty((B, N, 9), np.float32)
+    check(lib.ggs_loss_grad(_fp(g), B, N, Cc, lay, _fp(tgt), K, group, H, W, float(k_sigma), _fp(bg),
+                            C.byref(prm), _fp(loss), _fp(grad), device_index(device)), "ggs_loss_grad")
+    return loss, grad
+
+
 def encode(G_axes) -> np.ndarray:
     """encode.py:62-79 genome_to_renderer_batched (any leading shape, C ≥ 9) → [..., 9]."""
     g = as_f32(G_axes)
@@ -409,6 +481,29 @@ def render_vjp_device(device: int, stream: int, d_genomes: int, B: int, N: int, 
                                     H, W, float(k_sigma), _fp(_background3(background)),
                                     C.c_void_p(d_cot or None), C.c_void_p(d_grad or None)),
           "ggs_render_vjp_device")
+
+
+def image_loss_device(device: int, stream: int, d_img: int, B: int, d_targets: int, K: int, group: int, H: int,
+                      W: int, params, d_loss: int, d_cot: int = 0) -> None:
+    """Enqueue the image loss (d_img [B,H,W,3] against d_targets [K,H,W,3] -> d_loss [B] and,
+    unless 0, d_cot [B,H,W,3]) on `stream`."""
+    prm = loss_params_c(params)
+    check(lib.ggs_image_loss_device(device, C.c_void_p(stream), C.c_void_p(d_img or None), B,
+                                    C.c_void_p(d_targets or None), K, int(group), H, W, C.byref(prm),
+                                    C.c_void_p(d_loss or None), C.c_void_p(d_cot or None)),
+          "ggs_image_loss_device")
+
+
+def loss_grad_device(device: int, stream: int, d_genomes: int, B: int, N: int, Cc: int, layout: int,
+                     d_targets: int, K: int, group: int, H: int, W: int, k_sigma: float, params, d_loss: int,
+                     d_grad: int, background=(1.0, 1.0, 1.0)) -> None:
+    """Enqueue render -> image loss -> VJP (d_loss [B], d_grad [B,N,9]) on `stream`."""
+    prm = loss_params_c(params)
+    check(lib.ggs_loss_grad_device(device, C.c_void_p(stream), C.c_void_p(d_genomes or None), B, N, Cc,
+                                   int(layout), C.c_void_p(d_targets or None), K, int(group), H, W,
+                                   float(k_sigma), _fp(_background3(background)), C.byref(prm),
+                                   C.c_void_p(d_loss or None), C.c_void_p(d_grad or None)),
+          "ggs_loss_grad_device")
 
 
 def profile_enable(on: bool = True) -> None:

@@ -13,6 +13,11 @@ into ``genomes.grad``: ``backward`` hands ``grad_output`` to the renderer's
 vector-Jacobian product (ggs_render_vjp_device), again on torch's
 current stream with no host copy.
 
+``image_loss(img, targets, params)`` is the library's own L1 / MSE / SSIM loss [B]
+ of images [B,H,W,3]: ``forward`` computes loss and cotangent in one
+device call, ``backward`` scales the cotangent, so
+``image_loss(render_splats(g, H, W), t).sum().backward()`` needs no loss written in torch.
+
 torch is imported here, never by ``import ggs``.
 """
 from __future__ import annotations
@@ -140,3 +145,57 @@ def render_splats(genomes, H: int, W: int, *, k_sigma: float = 3.0, background=(
     if genomes.dim() == 2:
         return RenderSplats.apply(genomes[None], *args)[0]
     return RenderSplats.apply(genomes, *args)
+
+
+class ImageLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, targets, params, group):
+        if img.dim() != 4 or img.shape[3] != 3:
+            raise _lib.GGSInputError(f"img must be [B,H,W,3], got {tuple(img.shape)}")
+        B, H, W, _ = (int(v) for v in img.shape)
+        if targets.dim() != 4 or tuple(targets.shape[1:]) != (H, W, 3):
+            raise _lib.GGSInputError(f"targets must be [K,H,W,3] with (H, W) = {(H, W)}, got {tuple(targets.shape)}")
+        K = int(targets.shape[0])
+        x = img.detach().to(torch.float32).contiguous()
+        if x.is_cuda:
+            dev = x.device
+            t = targets.detach().to(device=dev, dtype=torch.float32).contiguous()
+            loss = torch.empty(B, dtype=torch.float32, device=dev)
+            cot = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+            _lib.ensure_init()
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                api.image_loss_device(dev.index or 0, stream, x.data_ptr(), B, t.data_ptr(), K, group, H, W, params,
+                                      loss.data_ptr(), cot.data_ptr())
+        else:
+            lo, co = api.image_loss(x, targets.detach(), params, group=group)
+            loss, cot = torch.from_numpy(lo), torch.from_numpy(co)
+        ctx.save_for_backward(cot)
+        ctx.in_dtype = img.dtype
+        return loss.to(img.dtype) if img.dtype != torch.float32 else loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        (cot,) = ctx.saved_tensors
+        g = cot * grad_output.to(cot.dtype)[:, None, None, None]
+        return g.to(ctx.in_dtype), None, None, None
+
+
+def image_loss(img, targets, params=None, group=None):
+    """The image loss [B] of ``img`` [B,H,W,3] ([H,W,3]: a scalar) against ``targets``
+    [K,H,W,3] (image b against target ``b // group``, default B // K) or [H,W,3] (one target
+    for all), differentiable with respect to ``img``; no gradient reaches the targets.
+    ``params``: ``ggs.LossParams`` (default 0.8 L1 + 0.2 (1 - SSIM))."""
+    p = api.LossParams() if params is None else api.LossParams(*params)
+    single = img.dim() == 3
+    x = img[None] if single else img
+    B = int(x.shape[0])
+    if targets.dim() == 3:
+        if group is not None:
+            raise _lib.GGSInputError("group= needs 4-D targets [K,H,W,3]")
+        targets, group = targets[None], B
+    elif group is None:
+        group = max(B // max(int(targets.shape[0]), 1), 1)
+    out = ImageLoss.apply(x, targets, p, int(group))
+    return out[0] if single else out

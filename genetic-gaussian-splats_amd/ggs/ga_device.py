@@ -524,17 +524,24 @@ class DeviceRefine:
     rates.  A 4-D ``target`` [K, H, W, 3] (``mask`` [K, H, W] or None) refines candidate
     b against image ``b // group`` in one session (ggs_refine_create_targets; ``group``
     defaults to B // K); what ``read`` returns for a candidate has the bits of a
-    session on that genome and image alone."""
+    session on that genome and image alone.
+
+    ``loss`` (an ``api.LossParams``; default None: the fitness above) descends the image
+    loss L1 / MSE / SSIM of DESIGN.md §8f instead (ggs_refine_create_loss): ``mask`` must
+    then be None, ``fitness`` / ``best_fits`` are the loss, ``background`` is the render's,
+    and a step is ``api.loss_grad`` followed by ``adam_step``, bit for bit."""
 
     def __init__(self, target, mask, genomes, *, lr, beta1: float = 0.9, beta2: float = 0.999,
                  eps: float = 1e-8, min_scale_splats: float, max_scale_splats: float,
                  k_sigma: float = 3.0, boost_only: bool = False, boost_beta: float = 1.0, device: int = 0,
-                 group: Optional[int] = None):
+                 group: Optional[int] = None, loss=None, background=(1.0, 1.0, 1.0)):
         x = _arr(genomes, np.float32)
         if x.ndim == 2:
             x = x[None]
         if x.ndim != 3 or x.shape[2] != 9:
             raise _lib.GGSInputError("the device refiner keeps [B, N, 9] genomes")
+        if loss is not None and mask is not None:
+            raise _lib.GGSInputError("the image loss takes no weight mask")
         B, N, _ = x.shape
         self.target = _arr(target, np.float32)
         many = self.target.ndim == 4
@@ -557,7 +564,18 @@ class DeviceRefine:
         h = C.c_void_p()
         # arguments are validated before the library looks for a device
         mask_p = None if self.mask is None else self.mask.ctypes.data_as(_f32p)
-        if many:
+        if loss is not None:
+            from .api import loss_params_c
+            K = self.target.shape[0] if many else 1
+            if group is None:
+                group = max(B // max(K, 1), 1) if many else B
+            lp = loss_params_c(loss)
+            bg = np.ascontiguousarray(np.broadcast_to(np.asarray(background, np.float32), (3,)))
+            check(lib.ggs_refine_create_loss(device, C.byref(cfg), C.byref(prm), C.byref(lp),
+                                             bg.ctypes.data_as(_f32p), self.target.ctypes.data_as(_f32p), K,
+                                             x.ctypes.data_as(_f32p), B, int(group), C.byref(h)),
+                  "ggs_refine_create_loss")
+        elif many:
             K = self.target.shape[0]
             if group is None:
                 group = max(B // max(K, 1), 1)

@@ -70,19 +70,23 @@ def adam_step(x, g, m, v, t: int, params: AdamParams):
 def refine(genomes, target, H: int, W: int, steps: int, *, k_sigma: float = 3.0, weight_mask=None,
            boost_only: bool = False, boost_beta: float = 1.0, lr: Optional[Sequence[float]] = None,
            beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, min_scale_splats: float = 3.0,
-           max_scale_splats: float = 0.1, device: int = 0, group: Optional[int] = None) -> Dict[str, np.ndarray]:
+           max_scale_splats: float = 0.1, device: int = 0, group: Optional[int] = None, loss=None,
+           background=(1.0, 1.0, 1.0)) -> Dict[str, np.ndarray]:
     """``steps`` Adam steps on [B,N,9] (or [N,9]) genomes against ``target`` on the
     device → ``DeviceRefine.read``'s dict: the final state and its fitness, and per
     candidate the best state seen (``best`` / ``best_fits``), which is what a polish
     keeps.  ``lr=None``: ``DEFAULT_LR``.  A 4-D ``target`` [K,H,W,3] (``weight_mask``
-    [K,H,W]) refines candidate b against image ``b // group`` in one session."""
+    [K,H,W]) refines candidate b against image ``b // group`` in one session.
+    ``loss`` (``ggs.LossParams``; default None: the fitness) descends the image loss
+    L1 / MSE / SSIM of the render against ``background`` instead."""
     from .ga_device import DeviceRefine
     tgt = np.ascontiguousarray(target, np.float32)
     if tgt.shape[-3:] != (int(H), int(W), 3) or tgt.ndim not in (3, 4):
         raise ValueError(f"target must be [H,W,3] or [K,H,W,3] with (H, W) = {(H, W)}, got {tuple(tgt.shape)}")
     s = DeviceRefine(tgt, weight_mask, genomes, lr=DEFAULT_LR if lr is None else lr, beta1=beta1, beta2=beta2,
                      eps=eps, min_scale_splats=min_scale_splats, max_scale_splats=max_scale_splats,
-                     k_sigma=k_sigma, boost_only=boost_only, boost_beta=boost_beta, device=device, group=group)
+                     k_sigma=k_sigma, boost_only=boost_only, boost_beta=boost_beta, device=device, group=group, loss=loss,
+                     background=background)
     try:
         s.run(int(steps))
         return s.read()

@@ -556,6 +556,43 @@ int ggs_render_vjp(const float* genomes, int64_t B, int32_t N, int32_t C, int32_
 int ggs_render_layout_device(int32_t device, void* stream, const float* d_genomes, int64_t B, int32_t N, int32_t C,
                              int32_t layout, int32_t H, int32_t W, float k_sigma, const float* bg, float* d_out_bhw3);
 
+/* ---- image losses ------------------------------------------------
+ * For candidate b with image x = img[b] [H,W,3] (what ggs_render_device writes) and
+ * target y = targets[b / group],
+ *   loss[b] = w_l1 mean|x - y| + w_mse mean (x - y)^2 + w_ssim (1 - mean SSIM(x, y))
+ * the means over all 3 H W values; SSIM per channel with the 11 x 11 separable
+ * Gaussian window (sigma 1.5, taps normalised in float64), zero padding, C1 = 0.01^2,
+ * C2 = 0.03^2 (the 3DGS / GaussianImage loss is w = (1 - lambda, 0, lambda)).
+ * cot[b] = d loss[b] / d x [H,W,3], with d|d|/dd = sign(d), sign(0) = 0.  Everything
+ * between the float32 inputs and the float32 outputs is float64.  Deterministic:
+ * reruns, other batches and a NULL cotangent give a candidate's loss the same bits.
+ * The group rule of ggs_fitness_device_planset (group >= 1, B % group == 0,
+ * B / group <= K), B, H or W < 1, null pointers (the cotangent may be NULL) and weights
+ * that are negative, not finite or all zero are GGS_EINVAL before any device is
+ * touched.  The device calls enqueue on `stream` and return; the host calls
+ * synchronise every stream they queued work on before returning, errors included. */
+typedef struct ggs_loss_params {
+    float w_l1, w_mse, w_ssim;       /* each >= 0 and finite, not all 0 */
+} ggs_loss_params;
+int ggs_image_loss_device(int32_t device, void* stream, const float* d_img_bhw3, int64_t B,
+                          const float* d_targets_khw3, int32_t K, int32_t group, int32_t H, int32_t W,
+                          const ggs_loss_params* p, float* d_loss_B, float* d_cot_bhw3 /* may be NULL */);
+int ggs_image_loss(const float* img_bhw3, int64_t B, const float* targets_khw3, int32_t K, int32_t group, int32_t H,
+                   int32_t W, const ggs_loss_params* p, float* loss_B, float* cot_bhw3 /* may be NULL */,
+                   int32_t device);
+/* loss [B] and d loss / d rows [B,N,9] in one call: ggs_render_layout_device, the image
+ * loss and ggs_render_vjp_device, issued as those entry points issue them (bytewise what
+ * the three calls give), the image and the cotangent in scratch the library owns
+ * (24 B per pixel of the batch).  Argument rules of ggs_render_vjp_device (GGS_ENOMEM
+ * for its 40 MiB partial budget) and of ggs_image_loss_device. */
+int ggs_loss_grad_device(int32_t device, void* stream, const float* d_genomes, int64_t B, int32_t N, int32_t C,
+                         int32_t layout, const float* d_targets_khw3, int32_t K, int32_t group, int32_t H, int32_t W,
+                         float k_sigma, const float* bg /* host, NULL = 1,1,1 */, const ggs_loss_params* p,
+                         float* d_loss_B, float* d_grad_BN9);
+int ggs_loss_grad(const float* genomes, int64_t B, int32_t N, int32_t C, int32_t layout, const float* targets_khw3,
+                  int32_t K, int32_t group, int32_t H, int32_t W, float k_sigma, const float* bg,
+                  const ggs_loss_params* p, float* loss_B, float* grad_BN9, int32_t device);
+
 /* ---- Adam refiner --------------------------------------------------------------
  * B candidates [B,N,9] refined side by side on the session's own stream.  Step t
  * (from 1) evaluates fitness and gradient g of the state x_t, makes x_t the
@@ -594,6 +631,14 @@ void ggs_refine_destroy(void* handle);
 int ggs_refine_create_targets(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p,
                               const float* targets_khw3, const float* masks_khw, int32_t K,
                               const float* genomes_BN9, int32_t B, int32_t group, void** handle);
+/* The refiner on the image loss above: step t evaluates ggs_loss_grad_device's loss and
+ * gradient of the axes-angle state (GGS_LAYOUT_AXES) against image b / group and the
+ * background bg (host, NULL = 1, 1, 1); fits is the loss.  The Adam update, the best-so-far
+ * rule and run / read / destroy are those above; cfg's fitness_mode and boost_beta are
+ * not read.  Argument errors as ggs_refine_create_targets and ggs_loss_grad_device. */
+int ggs_refine_create_loss(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p,
+                           const ggs_loss_params* loss, const float* bg, const float* targets_khw3, int32_t K,
+                           const float* genomes_BN9, int32_t B, int32_t group, void** handle);
 
 /* ---- memetic generations of an island group ----------------------
  * After the survivors of every generation g with g % every == 0 (g counts
