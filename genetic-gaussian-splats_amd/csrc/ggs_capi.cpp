@@ -1,30 +1,21 @@
 // C-ABI of libggs.so (declared in include/ggs.h): device contexts, pooled
 // workspaces, host<->device staging, multi-device fan-out, error reporting and
-// per-kernel event timing.  The kernels live in ggs_kernels.hip.
+// per-kernel event timing.  The kernels live in ggs_kernels.hip, the shared host
+// declarations in ggs_host.h, the device-resident sessions in ggs_sess_*.cpp.
 //
 // Reference boundary replaced here:
 //   render_splats_rgb_triton  modules/render.py:203-252  -> ggs_render / ggs_render_device
 //   fitness_many              modules/fitness.py:7-31    -> ggs_fitness / ggs_fitness_device
 //   (fitness_population fitness.py:34-47 and the list/tensor plumbing stay in Python)
-#include <hip/hip_runtime.h>
-#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
-#include <algorithm>
 #include <atomic>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
 
-#include "ggs_internal.h"
+#include "ggs_host.h"
 
 
 namespace ggs {
-namespace {
 
 thread_local std::string t_err;
 
@@ -38,32 +29,13 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-}  // namespace
-
 // thread-local ggs_last_error() message, for the other translation units (ggs_comm.cpp)
 int set_error(int code, const char* msg) {
     t_err = msg ? msg : "";
     return code;
 }
 
-namespace {
-
-#define GGS_HIP(call)                                                                            \
-    do {                                                                                         \
-        hipError_t e_ = (call);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(e_ == hipErrorOutOfMemory ? GGS_ENOMEM : GGS_EHIP, "%s: %s (%s:%d)",     \
-                        #call, hipGetErrorString(e_), __FILE__, __LINE__);                       \
-    } while (0)
-
 // ---- device buffers ---------------------------------------------------------
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
-
-// Grow `b` to at least `bytes`.  `st` is the stream that may still be using the
-// old allocation; it is synchronised before the free.
 int ensure(DevBuf& b, size_t bytes, hipStream_t st) {
     if (bytes <= b.cap) return GGS_OK;
     if (b.p) {
@@ -78,9 +50,6 @@ int ensure(DevBuf& b, size_t bytes, hipStream_t st) {
     return GGS_OK;
 }
 
-// ensure() for a counter block: a grown buffer is zeroed on `st` (the fused
-// finalize's per-candidate counters start at zero and every launch leaves them
-// at zero).
 int ensure_zeroed(DevBuf& b, size_t bytes, hipStream_t st) {
     if (bytes <= b.cap) return GGS_OK;
     int rc = ensure(b, bytes, st);
@@ -97,28 +66,23 @@ int ensure_zeroed(DevBuf& b, size_t bytes, hipStream_t st) {
 // -0.4 % and +17 MB of write traffic per launch, with one stream +0.1 %
 // (docs/EXPERIMENTS.md §14).  GGS_UNFUSED_FINALIZE=1 unfuses the GA too (A/B
 // switch, same bits).
-bool finalize_fused() {
+static bool finalize_fused() {
     static const bool off = getenv("GGS_UNFUSED_FINALIZE") && atoi(getenv("GGS_UNFUSED_FINALIZE")) != 0;
     return !off;
 }
 // Test switch: GGS_FITNESS_FOLD=1 folds the finalize into the fitness API's raster
 // too (read per call, so one test process can cover both paths; the GA's fold
 // under concurrent, uneven load is otherwise exercised only through GA sessions).
-bool fitness_api_fold() {
+static bool fitness_api_fold() {
     const char* v = getenv("GGS_FITNESS_FOLD");
     return v && atoi(v) != 0;
 }
 // A/B and test switch: GGS_STRIP_WORDS=0 keeps the raster's own cull from the bounds
 // where prep would hand it strip words (read per call; the same bits either way).
-bool strip_words_on() {
+static bool strip_words_on() {
     const char* v = getenv("GGS_STRIP_WORDS");
     return !(v && *v && atoi(v) == 0);
 }
-
-struct PinBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
 
 int ensure_pinned(PinBuf& b, size_t bytes) {
     if (bytes <= b.cap) return GGS_OK;
@@ -133,21 +97,8 @@ int ensure_pinned(PinBuf& b, size_t bytes) {
     return GGS_OK;
 }
 
-// Per-(device, stream) scratch used by one render/fitness pipeline.
-struct Workspace {
-    hipStream_t stream = nullptr;
-    DevBuf recs, bnds, partials, wpartials, order, plan, fctr;   // fctr: fused-finalize counters
-    DevBuf maskws;                    // target preparation / importance mask scratch (ggs_mask.hip)
-    DevBuf swords, smasks;            // strip words and masks, prep -> raster (StripWords)
-    DevBuf gf9, gi4, gpart, gout;     // fitness gradient: prep's stage outputs, strip partials, unwanted fitness
-    DevBuf lpart, limg, lcot;         // image loss: tile partials; ggs_loss_grad's image and cotangent
-    int order_H = -1, order_W = -1;   // (H, W) the tile order was built for
-    bool strips_ok = false;           // ... and whether its strip table holds that canvas
-    uint64_t plan_key = 0;            // inputs the plan was built from (0: none / volatile)
-};
-
 // Upload the centre-first raster dispatch order for (H, W) once per size.
-int ensure_tile_order(Workspace* w, int H, int W, hipStream_t st) {
+static int ensure_tile_order(Workspace* w, int H, int W, hipStream_t st) {
     if (w->order_H == H && w->order_W == W) return GGS_OK;
     const int n = raster_order_len(H, W);
     int rc;
@@ -180,24 +131,13 @@ int ensure_tile_order(Workspace* w, int H, int W, hipStream_t st) {
     return GGS_OK;
 }
 
-struct DevCtx {
-    int dev = 0;
-    int simds = 0;                 // CUs x 4 of dev (single-round raster ordering)
-    hipStream_t stream = nullptr;  // library-owned stream for the host API
-    std::mutex mu;
-    std::vector<std::unique_ptr<Workspace>> ws;
-    // host-API staging
-    DevBuf gen, out, target, mask, ggrad;   // ggrad: ggs_fitness_grad's [B,N,9]
-    DevBuf set_plan, set_wpart;            // ggs_fitness_grad_targets' own plan set
-    DevBuf prep_in, prep_tgt, prep_mask;   // ggs_targets_prepare / ggs_quantiles staging
-    DevBuf loss_img, loss_cot, loss_out;   // ggs_image_loss / ggs_loss_grad staging
-    PinBuf h_out;                  // the fitness scalars (render and genomes go straight to / from the caller)
-    uint64_t target_key = 0, mask_key = 0;
-    size_t target_bytes = 0, mask_bytes = 0;
-};
+namespace {
 
 std::mutex g_mu;
-std::vector<std::unique_ptr<DevCtx>> g_ctx;  // indexed by HIP device id
+// Indexed by HIP device id.  The registry is immortal (never destroyed): a context
+// owns device buffers, and no HIP call may run from a static destructor after
+// main() returns.  ggs_shutdown is the only place that releases contexts.
+auto& g_ctx = *new std::vector<std::unique_ptr<DevCtx>>;
 std::vector<int> g_active;                    // devices the host API fans out over
 bool g_inited = false;
 
@@ -214,30 +154,26 @@ double g_prof_ms[kProfKernels] = {};
 int64_t g_prof_n[kProfKernels] = {};
 const char* const kKernelNames[kProfKernels] = {"prep", "raster", "finalize", "select"};
 
-struct ProfScope {
-    bool on = false;
-    hipEvent_t a = nullptr, b = nullptr;
-    hipStream_t st;
-    int kernel;
-    ProfScope(hipStream_t s, int k) : st(s), kernel(k) {
-        {
-            std::lock_guard<std::mutex> lk(g_prof_mu);
-            on = g_prof_on;
-        }
-        if (on && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess)
-            (void)hipEventRecord(a, st);
-        else
-            on = false;
-    }
-    ~ProfScope() {
-        if (!on) return;
-        (void)hipEventRecord(b, st);
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        g_prof_pending.push_back({kernel, a, b});
-    }
-};
+}  // namespace
 
-void prof_drain_locked() {
+ProfScope::ProfScope(hipStream_t s, int k) : st(s), kernel(k) {
+    {
+        std::lock_guard<std::mutex> lk(g_prof_mu);
+        on = g_prof_on;
+    }
+    if (on && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess)
+        (void)hipEventRecord(a, st);
+    else
+        on = false;
+}
+ProfScope::~ProfScope() {
+    if (!on) return;
+    (void)hipEventRecord(b, st);
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    g_prof_pending.push_back({kernel, a, b});
+}
+
+static void prof_drain_locked() {
     for (auto& r : g_prof_pending) {
         float ms = 0.f;
         if (hipEventSynchronize(r.b) == hipSuccess && hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
@@ -250,13 +186,10 @@ void prof_drain_locked() {
     g_prof_pending.clear();
 }
 
-// raster (MODE 1) + finalize of B candidates: one launch when `fuse` (and allowed).
-// group > 0: plan / wpartials are a plan set's and candidate b is scored against
-// plan b / group.
 int raster_fitness(hipStream_t st, int simds, const SplatRec* recs, const int4* bnds, int B, int N, int H, int W,
                    const float4* plan, float* partials, const float* wpartials, int mode, const int* order,
-                   DevBuf& ctr, float* out, bool fuse, const unsigned char* dirty = nullptr,
-                   const float* clean = nullptr, int group = 0, const StripWords& sw = StripWords{}) {
+                   DevBuf& ctr, float* out, bool fuse, const unsigned char* dirty, const float* clean, int group,
+                   const StripWords& sw) {
     const float bg[3] = {1.f, 1.f, 1.f};  // fitness renders with the default background (fitness.py:15)
     int nTX;
     const int nTiles = raster_tiles(H, W, &nTX);
@@ -289,17 +222,7 @@ int raster_fitness(hipStream_t st, int simds, const SplatRec* recs, const int4* 
 }
 
 // ---- helpers ----------------------------------------------------------------------
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
+namespace {
 // Host API: every stream this call has queued work on — copies from or into the
 // caller's arrays included — is synchronised before the call returns, on error
 // returns too, so the caller's arrays are never touched after the call
@@ -370,12 +293,16 @@ int ctx_locked(int d, DevCtx** out) {
     return GGS_OK;
 }
 
+}  // namespace
+
 int get_ctx(int device, DevCtx** out) {
     std::lock_guard<std::mutex> lk(g_mu);
     const int rc = init_locked(0);
     if (rc < 0) return rc;
     return ctx_locked(device, out);
 }
+
+namespace {
 
 // The first n (<=0: all) devices of the active list, contexts created.
 int active_ctxs(int32_t n_devices, std::vector<DevCtx*>* out) {
@@ -393,6 +320,8 @@ int active_ctxs(int32_t n_devices, std::vector<DevCtx*>* out) {
     return GGS_OK;
 }
 
+}  // namespace
+
 Workspace* workspace_for(DevCtx* c, hipStream_t st) {
     for (auto& w : c->ws)
         if (w->stream == st) return w.get();
@@ -402,7 +331,6 @@ Workspace* workspace_for(DevCtx* c, hipStream_t st) {
 }
 
 // xxhash64-style content hash (target/mask upload cache)
-inline uint64_t rotl(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 uint64_t hash_bytes(const void* data, size_t n) {
     const uint64_t P1 = 0x9E3779B185EBCA87ull, P2 = 0xC2B2AE3D27D4EB4Full, P3 = 0x165667B19E3779F9ull;
     const unsigned char* p = (const unsigned char*)data;
@@ -445,7 +373,7 @@ int check_dims(int64_t B, int32_t N, int32_t C, int32_t H, int32_t W) {
 // ---- the device pipelines (ctx locked, device set) ----------------------------------
 // The workspace's strip-word buffers for a batch of B x N splats where the batch
 // qualifies and the switch is on (else *sw stays empty: the raster culls from bnds).
-int ensure_strip_words(Workspace* w, int64_t B, int N, int H, int W, hipStream_t st, StripWords* sw) {
+static int ensure_strip_words(Workspace* w, int64_t B, int N, int H, int W, hipStream_t st, StripWords* sw) {
     if (!strip_words_ok(N) || !strip_words_on()) return GGS_OK;
     int rc;
     if ((rc = ensure(w->swords, strip_words_bytes(B, N, H, W), st))) return rc;
@@ -457,16 +385,10 @@ int ensure_strip_words(Workspace* w, int64_t B, int N, int H, int W, hipStream_t
         sw->table = (const int*)w->order.p + raster_order_len(H, W);
     return GGS_OK;
 }
-int run_fitness_planned(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C,
-                        const float4* plan, const float* wpartials, int mode, int H, int W, float k,
-                        float* d_out, int group = 0);
 
-// plan_key: identifies (target contents, mask contents, mode, beta, H, W) when
-// the caller knows them to be unchanged since a previous call with the same key
-// (host API: content hashes; GA/SA sessions: immutable inputs); 0 = rebuild.
 int run_fitness(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C,
                 const float* d_target, const float* d_mask, int mode, float beta, int H, int W,
-                float k, float* d_out, uint64_t plan_key = 0) {
+                float k, float* d_out, uint64_t plan_key) {
     if (B == 0) return GGS_OK;
     Workspace* w = workspace_for(c, st);
     int nTX;
@@ -488,8 +410,6 @@ int run_fitness(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N,
                                (const float*)w->wpartials.p, mode, H, W, k, d_out);
 }
 
-// prep -> raster -> finalize against a ready target plan (group > 0: a plan set,
-// candidate b against plan b / group).
 int run_fitness_planned(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C,
                         const float4* plan, const float* wpartials, int mode, int H, int W, float k,
                         float* d_out, int group) {
@@ -516,9 +436,8 @@ int run_fitness_planned(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B
                           nullptr, group, sw);
 }
 
-// encode: the rows are axes-angle rows, prep encodes them first (GGS_LAYOUT_AXES)
 int run_render(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C, int H, int W,
-               float k, const float bg[3], float* d_img, bool encode = false) {
+               float k, const float bg[3], float* d_img, bool encode) {
     if (B == 0) return GGS_OK;
     Workspace* w = workspace_for(c, st);
     int rc;
@@ -647,8 +566,6 @@ int check_loss_dims(int64_t B, int32_t K, int32_t group, int32_t H, int32_t W) {
     return GGS_OK;
 }
 
-// loss [B] and, unless d_cot is null, the cotangent [B][H][W][3]; the tile partials are
-// the stream's workspace.
 int run_image_loss(DevCtx* c, hipStream_t st, const float* d_img, int64_t B, const float* d_targets, int group, int H,
                    int W, const ggs_loss_params& p, float* d_loss, float* d_cot) {
     Workspace* w = workspace_for(c, st);
@@ -668,8 +585,6 @@ int check_loss_grad(int64_t B, int32_t N, int32_t C, int32_t layout, int32_t K, 
     return rc;
 }
 
-// render -> image loss -> VJP, the three stages as their own entry points issue them;
-// d_img / d_cot [B][H][W][3] are the caller's scratch.
 int run_loss_grad(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C, int layout,
                   const float* d_targets, int group, int H, int W, float k, const float bg[3],
                   const ggs_loss_params& p, float* d_loss, float* d_grad, float* d_img, float* d_cot) {
@@ -679,11 +594,9 @@ int run_loss_grad(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int 
     return run_render_vjp(c, st, d_gen, B, N, C, layout, H, W, k, bg, d_cot, d_grad);
 }
 
-// Fitness (the existing prep -> raster -> finalize path, so ggs_fitness_device's
-// bits) and its gradient [B][N][9].  d_out may be null.
 int run_fitness_grad(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C, const float* d_target,
                      const float* d_mask, int mode, float beta, int H, int W, float k, float* d_out, float* d_grad,
-                     uint64_t plan_key = 0) {
+                     uint64_t plan_key) {
     Workspace* w = workspace_for(c, st);
     int rc;
     if (!d_out) {
@@ -696,9 +609,6 @@ int run_fitness_grad(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, i
                            0, d_grad);
 }
 
-// The same against ready plans: group == 0 one plan (ggs_fitness_device_planned's
-// bits), group > 0 a plan set (ggs_fitness_device_planset's).  d_targets / d_masks:
-// the raw arrays the plans were made from.
 int run_fitness_grad_planned(DevCtx* c, hipStream_t st, const float* d_gen, int64_t B, int N, int C,
                              const float4* plan, const float* wblocks, const float* d_targets, const float* d_masks,
                              int mode, float beta, int H, int W, int group, float k, float* d_out, float* d_grad) {
@@ -724,6 +634,8 @@ int check_grad_set(int64_t B, int32_t N, int32_t C, int32_t H, int32_t W, int32_
         return fail(GGS_EINVAL, "B / group = %lld images wanted, the set holds %d", (long long)(B / group), K);
     return GGS_OK;
 }
+
+namespace {
 
 // Split [0, B) into n contiguous shards of ceil(B/n) (the last ones shorter or
 // empty): equal-sized slots, so the fitness shards meet in one in-place RCCL
@@ -814,21 +726,13 @@ void ggs_shutdown(void) {
         std::lock_guard<std::mutex> cl(c->mu);
         (void)hipSetDevice(c->dev);
         (void)hipStreamSynchronize(c->stream);
-        for (auto& w : c->ws) {
+        for (auto& w : c->ws)
             if (w->stream) (void)hipStreamSynchronize(w->stream);
-            for (DevBuf* b : {&w->recs, &w->bnds, &w->partials, &w->wpartials, &w->order, &w->plan, &w->fctr, &w->maskws,
-                              &w->swords, &w->smasks, &w->gf9, &w->gi4, &w->gpart, &w->gout,
-                              &w->lpart, &w->limg, &w->lcot})
-                if (b->p) (void)hipFree(b->p);
-        }
-        for (DevBuf* b : {&c->gen, &c->out, &c->target, &c->mask, &c->ggrad, &c->set_plan, &c->set_wpart, &c->prep_in,
-                          &c->prep_tgt, &c->prep_mask, &c->loss_img, &c->loss_cot, &c->loss_out})
-            if (b->p) (void)hipFree(b->p);
-        for (PinBuf* b : {&c->h_out})
-            if (b->p) (void)hipHostFree(b->p);
+        // the workspaces and the staging free themselves here: device current, context locked
+        static_cast<CtxBuffers&>(*c) = CtxBuffers{};
         (void)hipStreamDestroy(c->stream);
     }
-    g_ctx.clear();
+    g_ctx.clear();      // the contexts own nothing by now
     g_active.clear();
     g_inited = false;
 }
@@ -901,17 +805,13 @@ int ggs_plan_create(int32_t device, void* stream, const float* d_target_hw3, con
     p->W = W;
     p->mode = mode;
     const hipStream_t st = (hipStream_t)stream;
-    auto bail = [&](int code) {
-        if (p->plan.p) (void)hipFree(p->plan.p);
-        if (p->wpartials.p) (void)hipFree(p->wpartials.p);
-        return code;
-    };
+    // (an error return frees the plan's buffers with it, before the lock is released)
     if ((rc = ensure(p->plan, plan_bytes(H, W), st)) ||
         (rc = ensure(p->wpartials, plan_wsum_bytes(H, W), st)))
-        return bail(rc);
+        return rc;
     if (launch_plan(st, d_target_hw3, d_mask_hw, mode, boost_beta, H, W, (float4*)p->plan.p,
                     (float*)p->wpartials.p) != hipSuccess)
-        return bail(fail(GGS_EHIP, "plan launch failed"));
+        return fail(GGS_EHIP, "plan launch failed");
     *plan = p.release();
     return GGS_OK;
 }
@@ -933,13 +833,9 @@ int ggs_fitness_device_planned(void* plan, void* stream, const float* d_genomes_
 void ggs_plan_destroy(void* plan) {
     if (!plan) return;
     TargetPlan* p = (TargetPlan*)plan;
-    {
-        std::lock_guard<std::mutex> lk(p->c->mu);
-        DeviceGuard dg(p->c->dev);
-        (void)hipDeviceSynchronize();    // streams that may still read the plan
-        if (p->plan.p) (void)hipFree(p->plan.p);
-        if (p->wpartials.p) (void)hipFree(p->wpartials.p);
-    }
+    std::lock_guard<std::mutex> lk(p->c->mu);
+    DeviceGuard dg(p->c->dev);
+    (void)hipDeviceSynchronize();    // streams that may still read the plan
     delete p;
 }
 
@@ -965,17 +861,12 @@ int ggs_planset_create(int32_t device, void* stream, const float* d_targets_khw3
     p->K = K;
     p->beta = boost_beta;
     const hipStream_t st = (hipStream_t)stream;
-    auto bail = [&](int code) {
-        if (p->plan.p) (void)hipFree(p->plan.p);
-        if (p->wpartials.p) (void)hipFree(p->wpartials.p);
-        return code;
-    };
     if ((rc = ensure(p->plan, (size_t)K * plan_bytes(H, W), st)) ||
         (rc = ensure(p->wpartials, (size_t)K * plan_wsum_bytes(H, W), st)))
-        return bail(rc);
+        return rc;
     if (launch_plan_set(st, d_targets_khw3, d_masks_khw, mode, boost_beta, H, W, K, (float4*)p->plan.p,
                         (float*)p->wpartials.p) != hipSuccess)
-        return bail(fail(GGS_EHIP, "plan launch failed"));
+        return fail(GGS_EHIP, "plan launch failed");
     *planset = p.release();
     return GGS_OK;
 }
@@ -1015,13 +906,9 @@ int ggs_fitness_grad_device_planset(void* planset, void* stream, const float* d_
 void ggs_planset_destroy(void* planset) {
     if (!planset) return;
     PlanSet* p = (PlanSet*)planset;
-    {
-        std::lock_guard<std::mutex> lk(p->c->mu);
-        DeviceGuard dg(p->c->dev);
-        (void)hipDeviceSynchronize();    // streams that may still read the plans
-        if (p->plan.p) (void)hipFree(p->plan.p);
-        if (p->wpartials.p) (void)hipFree(p->wpartials.p);
-    }
+    std::lock_guard<std::mutex> lk(p->c->mu);
+    DeviceGuard dg(p->c->dev);
+    (void)hipDeviceSynchronize();    // streams that may still read the plans
     delete p;
 }
 
@@ -1222,6 +1109,35 @@ uint64_t host_plan_key(uint64_t tkey, uint64_t mkey, float boost_beta, int mode,
              ((uint64_t)mode << 2) ^ ((uint64_t)H << 40) ^ ((uint64_t)W << 20)) & ~(1ull << 63)) | 1;
 }
 
+// Upload the caller's target or mask into its staging buffer (large enough) when the
+// content key or the byte count differs from what the buffer holds.
+int upload_if_changed(DevBuf& buf, uint64_t* held_key, size_t* held_bytes, const float* src, uint64_t key,
+                      size_t bytes, hipStream_t st) {
+    if (key == *held_key && bytes == *held_bytes) return GGS_OK;
+    GGS_HIP(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st));
+    *held_key = key;
+    *held_bytes = bytes;
+    return GGS_OK;
+}
+
+// A host call on one device: the context lock, the device guard, the context's stream
+// and, declared after the lock so that it drains while the lock is held, the drain
+// that synchronises the stream on every return.
+struct HostCall {
+    DevCtx* c;
+    std::lock_guard<std::mutex> lk;
+    DeviceGuard dg;
+    hipStream_t st;
+    StreamDrain drain;
+    explicit HostCall(DevCtx* ctx) : c(ctx), lk(ctx->mu), dg(ctx->dev), st(ctx->stream) {}
+    // the previous call's work is done with the staging; what follows is drained
+    int begin() {
+        GGS_HIP(hipStreamSynchronize(st));
+        drain.add(c->dev, st);
+        return GGS_OK;
+    }
+};
+
 // One device, host arrays in and out.  The content hashes of target and mask
 // (4 MB at 512^2: ~0.2 ms on one core) decide whether the device copies cached
 // from an earlier call are still right.  A GA passes the same arrays every
@@ -1269,14 +1185,10 @@ int fitness_one_device_speculative(DevCtx* c, const float* genomes_axes, int64_t
     if ((rc = drain.drain())) return rc;
     if (tkey != c->target_key || mkey != mkey_c) {            // changed: redo with the new inputs
         drain.add(c->dev, st);
-        if (tkey != c->target_key) {
-            GGS_HIP(hipMemcpyAsync(c->target.p, target_hw3, tbytes, hipMemcpyHostToDevice, st));
-            c->target_key = tkey;
-        }
-        if (mask_hw && mkey != c->mask_key) {
-            GGS_HIP(hipMemcpyAsync(c->mask.p, mask_hw, mbytes, hipMemcpyHostToDevice, st));
-            c->mask_key = mkey;
-        }
+        if ((rc = upload_if_changed(c->target, &c->target_key, &c->target_bytes, target_hw3, tkey, tbytes, st)) ||
+            (mask_hw &&
+             (rc = upload_if_changed(c->mask, &c->mask_key, &c->mask_bytes, mask_hw, mkey, mbytes, st))))
+            return rc;
         if ((rc = evaluate(tkey, mkey))) return rc;
         if ((rc = drain.drain())) return rc;
     }
@@ -1331,20 +1243,12 @@ int ggs_fitness(const float* genomes_axes, int64_t B, int32_t N, int32_t C, cons
         if ((rc = ensure(c->out, sizeof(float) * (size_t)per * nd, st))) return rc;
         if ((rc = ensure_pinned(c->h_out, sizeof(float) * (size_t)(gather ? B : nb)))) return rc;
         if (nb == 0) continue;
-        if ((rc = ensure(c->target, tbytes, st))) return rc;
-        if (tkey != c->target_key || tbytes != c->target_bytes) {
-            GGS_HIP(hipMemcpyAsync(c->target.p, target_hw3, tbytes, hipMemcpyHostToDevice, st));
-            c->target_key = tkey;
-            c->target_bytes = tbytes;
-        }
-        if (mask_hw) {
-            if ((rc = ensure(c->mask, mbytes, st))) return rc;
-            if (mkey != c->mask_key || mbytes != c->mask_bytes) {
-                GGS_HIP(hipMemcpyAsync(c->mask.p, mask_hw, mbytes, hipMemcpyHostToDevice, st));
-                c->mask_key = mkey;
-                c->mask_bytes = mbytes;
-            }
-        }
+        if ((rc = ensure(c->target, tbytes, st)) ||
+            (rc = upload_if_changed(c->target, &c->target_key, &c->target_bytes, target_hw3, tkey, tbytes, st)))
+            return rc;
+        if (mask_hw && ((rc = ensure(c->mask, mbytes, st)) ||
+                        (rc = upload_if_changed(c->mask, &c->mask_key, &c->mask_bytes, mask_hw, mkey, mbytes, st))))
+            return rc;
         const size_t gbytes = sizeof(float) * row * (size_t)nb;
         if ((rc = ensure(c->gen, std::max<size_t>(gbytes, 4), st))) return rc;
         GGS_HIP(hipStreamSynchronize(st));  // the previous call's work is done with c->gen
@@ -1399,26 +1303,15 @@ int ggs_fitness_grad(const float* genomes_axes, int64_t B, int32_t N, int32_t C,
     const size_t gbytes = sizeof(float) * (size_t)N * C * (size_t)B, dbytes = sizeof(float) * 9 * (size_t)N * (size_t)B;
     const uint64_t tkey = hash_bytes(target_hw3, tbytes);
     const uint64_t mkey = mask_hw ? hash_bytes(mask_hw, mbytes) : 0;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard dg(c->dev);
-    hipStream_t st = c->stream;
-    StreamDrain drain;                  // after the context lock: drained on every return
+    HostCall hc(c);
+    const hipStream_t st = hc.st;
     if ((rc = ensure(c->out, sizeof(float) * (size_t)B, st)) || (rc = ensure(c->ggrad, dbytes, st)) ||
         (rc = ensure(c->target, tbytes, st)) || (mask_hw && (rc = ensure(c->mask, mbytes, st))) ||
-        (rc = ensure(c->gen, gbytes, st)))
+        (rc = ensure(c->gen, gbytes, st)) || (rc = hc.begin()))
         return rc;
-    GGS_HIP(hipStreamSynchronize(st));  // the previous call's work is done with c->gen
-    drain.add(c->dev, st);
-    if (tkey != c->target_key || tbytes != c->target_bytes) {
-        GGS_HIP(hipMemcpyAsync(c->target.p, target_hw3, tbytes, hipMemcpyHostToDevice, st));
-        c->target_key = tkey;
-        c->target_bytes = tbytes;
-    }
-    if (mask_hw && (mkey != c->mask_key || mbytes != c->mask_bytes)) {
-        GGS_HIP(hipMemcpyAsync(c->mask.p, mask_hw, mbytes, hipMemcpyHostToDevice, st));
-        c->mask_key = mkey;
-        c->mask_bytes = mbytes;
-    }
+    if ((rc = upload_if_changed(c->target, &c->target_key, &c->target_bytes, target_hw3, tkey, tbytes, st)) ||
+        (mask_hw && (rc = upload_if_changed(c->mask, &c->mask_key, &c->mask_bytes, mask_hw, mkey, mbytes, st))))
+        return rc;
     GGS_HIP(hipMemcpyAsync(c->gen.p, genomes_axes, gbytes, hipMemcpyHostToDevice, st));
     if ((rc = run_fitness_grad(c, st, (const float*)c->gen.p, B, N, C, (const float*)c->target.p,
                                mask_hw ? (const float*)c->mask.p : nullptr, mode, boost_beta, H, W, k_sigma,
@@ -1427,7 +1320,7 @@ int ggs_fitness_grad(const float* genomes_axes, int64_t B, int32_t N, int32_t C,
     GGS_HIP(hipMemcpyAsync(out_B, c->out.p, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st));
     GGS_HIP(hipMemcpyAsync(grad_BN9, c->ggrad.p, dbytes, hipMemcpyDeviceToHost, st));
     if (inject_fail_after(1)) return fail(GGS_EHIP, "injected failure after device 1's work (test hook)");
-    return drain.drain();
+    return hc.drain.drain();
 }
 
 int ggs_render_vjp(const float* genomes, int64_t B, int32_t N, int32_t C, int32_t layout, int32_t H, int32_t W,
@@ -1440,22 +1333,19 @@ int ggs_render_vjp(const float* genomes, int64_t B, int32_t N, int32_t C, int32_
     const float bg1[3] = {1.f, 1.f, 1.f};
     const size_t vbytes = sizeof(float) * 3 * (size_t)H * W * (size_t)B;
     const size_t gbytes = sizeof(float) * (size_t)N * C * (size_t)B, dbytes = sizeof(float) * 9 * (size_t)N * (size_t)B;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard dg(c->dev);
-    hipStream_t st = c->stream;
-    StreamDrain drain;                  // after the context lock: drained on every return
+    HostCall hc(c);
+    const hipStream_t st = hc.st;
     // the cotangent is staged in c->out, the render host call's image buffer
-    if ((rc = ensure(c->out, vbytes, st)) || (rc = ensure(c->ggrad, dbytes, st)) || (rc = ensure(c->gen, gbytes, st)))
+    if ((rc = ensure(c->out, vbytes, st)) || (rc = ensure(c->ggrad, dbytes, st)) || (rc = ensure(c->gen, gbytes, st)) ||
+        (rc = hc.begin()))
         return rc;
-    GGS_HIP(hipStreamSynchronize(st));  // the previous call's work is done with the staging
-    drain.add(c->dev, st);
     GGS_HIP(hipMemcpyAsync(c->gen.p, genomes, gbytes, hipMemcpyHostToDevice, st));
     GGS_HIP(hipMemcpyAsync(c->out.p, cot_bhw3, vbytes, hipMemcpyHostToDevice, st));
     if ((rc = run_render_vjp(c, st, (const float*)c->gen.p, B, N, C, layout, H, W, k_sigma, bg ? bg : bg1,
                              (const float*)c->out.p, (float*)c->ggrad.p)))
         return rc;
     GGS_HIP(hipMemcpyAsync(grad_BN9, c->ggrad.p, dbytes, hipMemcpyDeviceToHost, st));
-    return drain.drain();
+    return hc.drain.drain();
 }
 
 int ggs_image_loss(const float* img_bhw3, int64_t B, const float* targets_khw3, int32_t K, int32_t group, int32_t H,
@@ -1468,15 +1358,12 @@ int ggs_image_loss(const float* img_bhw3, int64_t B, const float* targets_khw3, 
     if ((rc = get_ctx(device, &c))) return rc;
     const size_t plane = sizeof(float) * 3 * (size_t)H * W;
     const size_t vbytes = plane * (size_t)B, tbytes = plane * (size_t)K;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard dg(c->dev);
-    hipStream_t st = c->stream;
-    StreamDrain drain;                  // after the context lock: drained on every return
+    HostCall hc(c);
+    const hipStream_t st = hc.st;
     if ((rc = ensure(c->loss_img, vbytes, st)) || (cot_bhw3 && (rc = ensure(c->loss_cot, vbytes, st))) ||
-        (rc = ensure(c->loss_out, sizeof(float) * (size_t)B, st)) || (rc = ensure(c->target, tbytes, st)))
+        (rc = ensure(c->loss_out, sizeof(float) * (size_t)B, st)) || (rc = ensure(c->target, tbytes, st)) ||
+        (rc = hc.begin()))
         return rc;
-    GGS_HIP(hipStreamSynchronize(st));  // the previous call's work is done with the staging
-    drain.add(c->dev, st);
     // the staging no longer holds what the single-target calls' content keys describe
     c->target_key = 0;
     c->target_bytes = 0;
@@ -1488,7 +1375,7 @@ int ggs_image_loss(const float* img_bhw3, int64_t B, const float* targets_khw3, 
         return rc;
     GGS_HIP(hipMemcpyAsync(loss_B, c->loss_out.p, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st));
     if (cot_bhw3) GGS_HIP(hipMemcpyAsync(cot_bhw3, d_cot, vbytes, hipMemcpyDeviceToHost, st));
-    return drain.drain();
+    return hc.drain.drain();
 }
 
 int ggs_loss_grad(const float* genomes, int64_t B, int32_t N, int32_t C, int32_t layout, const float* targets_khw3,
@@ -1503,16 +1390,13 @@ int ggs_loss_grad(const float* genomes, int64_t B, int32_t N, int32_t C, int32_t
     const size_t plane = sizeof(float) * 3 * (size_t)H * W;
     const size_t vbytes = plane * (size_t)B, tbytes = plane * (size_t)K;
     const size_t gbytes = sizeof(float) * (size_t)N * C * (size_t)B, dbytes = sizeof(float) * 9 * (size_t)N * (size_t)B;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard dg(c->dev);
-    hipStream_t st = c->stream;
-    StreamDrain drain;                  // after the context lock: drained on every return
+    HostCall hc(c);
+    const hipStream_t st = hc.st;
     if ((rc = ensure(c->loss_img, vbytes, st)) || (rc = ensure(c->loss_cot, vbytes, st)) ||
         (rc = ensure(c->loss_out, sizeof(float) * (size_t)B, st)) || (rc = ensure(c->target, tbytes, st)) ||
-        (rc = ensure(c->gen, gbytes, st)) || (rc = ensure(c->ggrad, dbytes, st)))
+        (rc = ensure(c->gen, gbytes, st)) || (rc = ensure(c->ggrad, dbytes, st)) ||
+        (rc = hc.begin()))
         return rc;
-    GGS_HIP(hipStreamSynchronize(st));  // the previous call's work is done with the staging
-    drain.add(c->dev, st);
     c->target_key = 0;
     c->target_bytes = 0;
     GGS_HIP(hipMemcpyAsync(c->gen.p, genomes, gbytes, hipMemcpyHostToDevice, st));
@@ -1523,7 +1407,7 @@ int ggs_loss_grad(const float* genomes, int64_t B, int32_t N, int32_t C, int32_t
         return rc;
     GGS_HIP(hipMemcpyAsync(loss_B, c->loss_out.p, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st));
     GGS_HIP(hipMemcpyAsync(grad_BN9, c->ggrad.p, dbytes, hipMemcpyDeviceToHost, st));
-    return drain.drain();
+    return hc.drain.drain();
 }
 
 int ggs_fitness_grad_targets(const float* genomes_axes, int64_t B, int32_t N, int32_t C, const float* targets_khw3,
@@ -1538,17 +1422,13 @@ int ggs_fitness_grad_targets(const float* genomes_axes, int64_t B, int32_t N, in
     DevCtx* c = cs[0];
     const size_t tbytes = sizeof(float) * 3 * (size_t)H * W * (size_t)K, mbytes = sizeof(float) * (size_t)H * W * (size_t)K;
     const size_t gbytes = sizeof(float) * (size_t)N * C * (size_t)B, dbytes = sizeof(float) * 9 * (size_t)N * (size_t)B;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard dg(c->dev);
-    hipStream_t st = c->stream;
-    StreamDrain drain;                  // after the context lock: drained on every return
+    HostCall hc(c);
+    const hipStream_t st = hc.st;
     if ((rc = ensure(c->out, sizeof(float) * (size_t)B, st)) || (rc = ensure(c->ggrad, dbytes, st)) ||
         (rc = ensure(c->target, tbytes, st)) || (masks_khw && (rc = ensure(c->mask, mbytes, st))) ||
         (rc = ensure(c->gen, gbytes, st)) || (rc = ensure(c->set_plan, (size_t)K * plan_bytes(H, W), st)) ||
-        (rc = ensure(c->set_wpart, (size_t)K * plan_wsum_bytes(H, W), st)))
+        (rc = ensure(c->set_wpart, (size_t)K * plan_wsum_bytes(H, W), st)) || (rc = hc.begin()))
         return rc;
-    GGS_HIP(hipStreamSynchronize(st));  // the previous call's work is done with the staging
-    drain.add(c->dev, st);
     // the staging no longer holds what the single-target calls' content keys describe
     c->target_key = c->mask_key = 0;
     c->target_bytes = c->mask_bytes = 0;
@@ -1564,7 +1444,7 @@ int ggs_fitness_grad_targets(const float* genomes_axes, int64_t B, int32_t N, in
         return rc;
     GGS_HIP(hipMemcpyAsync(out_B, c->out.p, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st));
     GGS_HIP(hipMemcpyAsync(grad_BN9, c->ggrad.p, dbytes, hipMemcpyDeviceToHost, st));
-    return drain.drain();
+    return hc.drain.drain();
 }
 
 int ggs_render(const float* genomes, int64_t B, int32_t N, int32_t C, int32_t H, int32_t W,
@@ -1628,10 +1508,7 @@ static int stage_call(bool encode, const float* in, int64_t S, int32_t C, int32_
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard dg(c->dev);
     hipStream_t st = c->stream;
-    struct Scratch {
-        void* p = nullptr;
-        ~Scratch() { if (p) (void)hipFree(p); }
-    } din, dout;
+    DevBuf din, dout;      // exact-size scratch of this call, freed on return
     const size_t ib = sizeof(float) * (size_t)S * C, ob = (f9 ? 13 : 9) * sizeof(float) * (size_t)S;
     GGS_HIP(hipMalloc(&din.p, ib));
     GGS_HIP(hipMalloc(&dout.p, ob));
@@ -1671,10 +1548,7 @@ int ggs_detmath_eval(int32_t fn, const float* x, const float* y, int64_t n, floa
     DevCtx* c = cs[0];
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard dg(c->dev);
-    struct Scratch {
-        void* p = nullptr;
-        ~Scratch() { if (p) (void)hipFree(p); }
-    } dx, dy, dout;
+    DevBuf dx, dy, dout;      // exact-size scratch of this call, freed on return
     const size_t nb = sizeof(float) * (size_t)n;
     GGS_HIP(hipMalloc(&dx.p, nb));
     GGS_HIP(hipMalloc(&dout.p, nb));
@@ -1717,512 +1591,61 @@ void ggs_profile_reset(void) {
     }
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// device-resident GA session (ggs_ga_*; kernels in ggs_ga.hip)
-// ---------------------------------------------------------------------------
-namespace ggs {
-namespace {
-
-// Target-plan cache keys of sessions (their target/mask never change): unique
-// for the process lifetime, top bit set (host-API content keys have it clear).
-std::atomic<uint64_t> g_session_ids{0};
-uint64_t new_plan_id() { return (1ull << 63) | ++g_session_ids; }
-
-struct GaSession {
-    uint64_t plan_id = new_plan_id();
+int ggs_workspace_count(int32_t device) {
     DevCtx* c = nullptr;
-    hipStream_t st = nullptr;
-    ggs_ga_config cfg{};
-    int P = 0, N = 0, cur = 0, nTiles = 0;
-    DevBuf pop[2], fits[2], off[2], off_fits, src, target, mask, best_ind, best_fit, best_src,
-        best_upd, curves, draws;
-    DevBuf elite[2];               // elite[cur]: rows of pop[cur] by fitness rank (the breed's row map)
-    int ocur = 0;                  // off[ocur]: the offspring evaluated last
-    bool pending = false;          // their survivors / gather not applied yet (ga_flush)
-    DevBuf recs, bnds, partials, plan, wpart, order, fctr;   // the generation's fused pipeline
-    int64_t n_curves = 0, curves_cap = 0;
-    void* comm = nullptr;          // ggs_ga_set_comm: offspring fitness sharded over ranks
-    int nranks = 1, rank = 0;
-    uint64_t fingerprint = 0;      // hash of (config, target, mask, initial population)
-};
-
-double anneal_factor(int gen, int total, int kind) {          // utils.py:14-27
-    const int g = std::max(0, std::min(gen, total));
-    const double p = (double)g / (double)std::max(1, total);
-    double raw;
-    if (kind == 1) raw = 0.5 * (1.0 + cos(M_PI * p));
-    else if (kind == 2) raw = pow(pow(0.2, 1.0 / (double)std::max(1, total)), (double)g);
-    else raw = 1.0 - p;
-    return std::max(0.0, raw);
-}
-
-GaParamsDev ga_params(const ggs_ga_config& c, int gen, int total) {   // build_mut_sigma
-    const double f = anneal_factor(gen, total, c.schedule);
-    float sig[6];
-    for (int k = 0; k < 6; ++k)
-        sig[k] = (float)(c.sig_min[k] + f * (c.sig_max[k] - c.sig_min[k]));
-    GaParamsDev p{};
-    p.sig_xy = sig[0]; p.sig_alog = sig[1]; p.sig_blog = sig[2]; p.sig_theta = sig[3];
-    p.sig_rgb = sig[4]; p.sig_alpha = sig[5];
-    p.mutpb = c.mutpb; p.cxpb = c.cxpb; p.tour_k = c.tour_k;
-    p.log_lo = c.scale_log_lo; p.log_hi = c.scale_log_hi;
-    return p;
-}
-
-GaBestDev ga_best(GaSession* s) {
-    return {(double*)s->best_fit.p, (int*)s->best_src.p, (int*)s->best_upd.p, (float*)s->best_ind.p};
-}
-
-// Row n of a session's curves [cap][3] on the device, grown (doubling) when full.
-int curves_row(DevBuf& curves, int64_t n, int64_t* cap_io, hipStream_t st, double** row) {
-    if (n >= *cap_io) {
-        const int64_t cap = std::max<int64_t>(64, *cap_io * 2);
-        DevBuf nb;
-        GGS_HIP(hipMalloc(&nb.p, sizeof(double) * 3 * cap));
-        nb.cap = sizeof(double) * 3 * cap;
-        if (curves.p) {
-            GGS_HIP(hipMemcpyAsync(nb.p, curves.p, sizeof(double) * 3 * n, hipMemcpyDeviceToDevice, st));
-            GGS_HIP(hipStreamSynchronize(st));
-            GGS_HIP(hipFree(curves.p));
-        }
-        curves = nb;
-        *cap_io = cap;
-    }
-    *row = (double*)curves.p + 3 * n;
-    return GGS_OK;
-}
-
-int ga_curves_row(GaSession* s, double** row) {
-    return curves_row(s->curves, s->n_curves, &s->curves_cap, s->st, row);
-}
-
-// Upload one generation's explicit draws into s->draws; returns device views.
-int ga_upload_draws(DevBuf& buf, hipStream_t st, int64_t P, int64_t N, int64_t K, bool mutation_only,
-                    const ggs_ga_draws* h, GaDrawsDev* d) {
-    const int64_t np2 = (P + 1) / 2;
-    struct Seg { const void* src; int64_t bytes; const void** dst; };
-    Seg segs[] = {
-        {h->tour_idx, 4 * P * K, (const void**)&d->tour_idx}, {h->perm, 4 * P, (const void**)&d->perm},
-        {h->cx, 4 * np2, (const void**)&d->cx}, {h->cx_u, 4 * np2 * N, (const void**)&d->cx_u},
-        {h->u_xy, 8 * P * N, (const void**)&d->u_xy}, {h->u_ab, 8 * P * N, (const void**)&d->u_ab},
-        {h->u_t, 4 * P * N, (const void**)&d->u_t}, {h->u_rgb, 4 * P * N, (const void**)&d->u_rgb},
-        {h->u_a, 4 * P * N, (const void**)&d->u_a}, {h->k_color, 4 * P, (const void**)&d->k_color},
-        {h->k_xy, 4 * P, (const void**)&d->k_xy}, {h->k_ab, 4 * P, (const void**)&d->k_ab},
-        {h->k_t, 4 * P, (const void**)&d->k_t}, {h->n_xy, 8 * P * N, (const void**)&d->n_xy},
-        {h->n_ab, 8 * P * N, (const void**)&d->n_ab}, {h->n_t, 4 * P * N, (const void**)&d->n_t},
-        {h->n_rgba, 16 * P * N, (const void**)&d->n_rgba}, {h->swap_i, 4 * P, (const void**)&d->swap_i},
-        {h->swap_pick, 4 * P, (const void**)&d->swap_pick}, {h->swap_u, 8 * P, (const void**)&d->swap_u},
-    };
-    const int first = mutation_only ? 4 : 0;   // SA: no selection / crossover draws
-    int64_t total = 0;
-    for (int k = first; k < (int)(sizeof segs / sizeof segs[0]); ++k) {
-        if (!segs[k].src) return fail(GGS_EINVAL, "every draws array is required");
-        total += (segs[k].bytes + 255) & ~(int64_t)255;
-    }
-    int rc;
-    if ((rc = ensure(buf, (size_t)total, st))) return rc;
-    GGS_HIP(hipStreamSynchronize(st));   // the previous launch may still read the buffer
-    char* base = (char*)buf.p;
-    for (int k = first; k < (int)(sizeof segs / sizeof segs[0]); ++k) {
-        const Seg& g = segs[k];
-        GGS_HIP(hipMemcpyAsync(base, g.src, (size_t)g.bytes, hipMemcpyHostToDevice, st));
-        *g.dst = base;
-        base += (g.bytes + 255) & ~(int64_t)255;
-    }
-    return GGS_OK;
-}
-
-// Survivors + gather of the generation evaluated last (algorithm.py:129-155):
-// population, fitness, best and curves as of the end of that generation.  A
-// generation leaves them pending; the next generation's breed applies them
-// itself (fused), anything reading the session state calls this first.
-int ga_flush(GaSession* s) {
-    if (!s->pending) return GGS_OK;
-    const int P = s->P, N = s->N, nxt = 1 - s->cur;
-    double* row;
-    int rc;
-    if ((rc = ga_curves_row(s, &row))) return rc;
-    // (FitReduce-fused survivors measured slower: 33.7 us vs 19 + 4.1 separately)
-    GGS_HIP(launch_ga_survivors(s->st, (const float*)s->fits[s->cur].p, (const float*)s->off_fits.p, P,
-                                s->cfg.elite_k, (int*)s->src.p, (float*)s->fits[nxt].p, ga_best(s), row, 0,
-                                FitReduce{}, (int*)s->elite[nxt].p));
-    GGS_HIP(launch_ga_gather(s->st, (const float*)s->pop[s->cur].p, (const float*)s->off[s->ocur].p, P, N,
-                             (const int*)s->src.p, (float*)s->pop[nxt].p, ga_best(s), 0));
-    s->cur = nxt;
-    s->n_curves += 1;
-    s->pending = false;
-    return GGS_OK;
-}
-
-// The fused breed (survivors + gather of the previous generation inside the
-// variation kernel: 3 launches per generation instead of 5) up to this population.
-bool ga_fused(const GaSession* s) {
-    static const bool off = getenv("GGS_GA_UNFUSED") && atoi(getenv("GGS_GA_UNFUSED")) != 0;
-    return !off && s->P <= ga_breed_max_population();
-}
-
-int ga_generation(GaSession* s, int gen, int total, const ggs_ga_draws* hd) {
-    GaDrawsDev d{};
-    int rc;
-    if (hd && (rc = ga_upload_draws(s->draws, s->st, s->P, s->N, s->cfg.tour_k, false, hd, &d))) return rc;
-    const int P = s->P, N = s->N;
-    const GaParamsDev prm = ga_params(s->cfg, gen, total);
-    const ggs_ga_config& c = s->cfg;
-    const int onew = 1 - s->ocur;
-    // per generation: breed (survivors + gather of the previous generation, then
-    // variation + prep of the offspring), raster, finalize [, all-gather]
-    // Only offspring[:P - E] survive (algorithm.py:140-141: the next generation is the
-    // E elites + the first P - E offspring, fitnesses likewise); the last E offspring's
-    // fitness is never read (survivors, fused breed, best, curves), so they are bred
-    // (their draws keep the trajectory) but not evaluated.
-    const int Pe = P - (c.elite_k < 1 ? 1 : c.elite_k);
-    // this rank's contiguous shard of the evaluated offspring (all of them on one GPU);
-    // every rank bred all P offspring above with the same draws
-    const int per = (Pe + s->nranks - 1) / s->nranks;
-    const int b0 = std::min(Pe, s->rank * per), nb = std::min(Pe, b0 + per) - b0;
-    if (s->pending && ga_fused(s)) {
-        const int nxt = 1 - s->cur;
-        double* row;
-        if ((rc = ga_curves_row(s, &row))) return rc;
-        BreedDev br{(const float*)s->pop[s->cur].p, (const float*)s->fits[s->cur].p,
-                    (const float*)s->off[s->ocur].p, (const float*)s->off_fits.p,
-                    (const int*)s->elite[s->cur].p, (int*)s->elite[nxt].p, (float*)s->pop[nxt].p,
-                    (float*)s->fits[nxt].p, row, ga_best(s), c.elite_k};
-        {
-            ProfScope ps(s->st, 0);
-            GGS_HIP(launch_ga_variation(s->st, nullptr, nullptr, P, N, prm, d, c.seed, gen, (float*)s->off[onew].p,
-                                        P, (SplatRec*)s->recs.p, (int4*)s->bnds.p, c.H, c.W, c.k_sigma, nullptr,
-                                        nullptr, &br));
-        }
-        s->cur = nxt;
-        s->n_curves += 1;
-    } else {
-        if ((rc = ga_flush(s))) return rc;
-        ProfScope ps(s->st, 0);
-        GGS_HIP(launch_ga_variation(s->st, (const float*)s->pop[s->cur].p, (const float*)s->fits[s->cur].p,
-                                    P, N, prm, d, c.seed, gen, (float*)s->off[onew].p, P, (SplatRec*)s->recs.p,
-                                    (int4*)s->bnds.p, c.H, c.W, c.k_sigma));
-    }
-    s->ocur = onew;
-    s->pending = true;
-    if (nb > 0 && (rc = raster_fitness(s->st, s->c->simds, (const SplatRec*)s->recs.p + (int64_t)b0 * N,
-                                       (const int4*)s->bnds.p + (int64_t)b0 * N, nb, N, c.H, c.W,
-                                       (const float4*)s->plan.p, (float*)s->partials.p, (const float*)s->wpart.p,
-                                       c.fitness_mode, (const int*)s->order.p, s->fctr,
-                                       (float*)s->off_fits.p + b0, true)))
-        return rc;
-    if (s->comm && per > 0) {   // one in-place all-gather of the shards' fitness scalars (RCCL, same stream)
-        float* of = (float*)s->off_fits.p;
-        if ((rc = ggs_comm_allgather(s->comm, s->st, of + (int64_t)s->rank * per, of, per, 0, nullptr)))
-            return rc;
-    }
-    return GGS_OK;
-}
-
-// The SA state keeps, besides the current genome, its splat records and its
-// per-strip partials: a neighbour is then evaluated incrementally — only the
-// strips a changed splat (old or new AABB) touches are rasterised, the others
-// keep the current partial (bit-identical to a full evaluation: same cull list,
-// same blend order).  annealing.py:121-146 re-renders the whole canvas per try.
-struct SaSession {
-    uint64_t plan_id = new_plan_id();
-    DevCtx* c = nullptr;
-    hipStream_t st = nullptr;
-    ggs_ga_config cfg{};
-    int N = 0, cap = 0, last_n = 0, nTiles = 0;
-    bool incremental = false;   // measured slower at every SA config tried
-    int dirty_rule = 1;         // 1: a splat is changed when its raster record is; 0: its genes (GGS_SA_DIRTY_RULE)
-    // cur_recs / cur_part describe the current state (create evaluates them, commit and
-    // an incremental device run install them); a non-incremental ggs_sa_run may
-    // accept neighbours without installing them
-    bool cur_cache_valid = true;
-    DevBuf curr, best, nb, nb_fits, target, mask, draws;
-    DevBuf cur_recs, nb_recs, nb_bnds, cur_part, nb_part, dirty, plan, wpart, order, counters, fctr;
-    DevBuf loop, sit, curves;       // device SA loop (ggs_sa_run): state, per-iteration table, curves
-    DevBuf flags, sizes;            // ... and its mutation scratch (per-try mask-group flags, splat sizes)
-    float* h_fits = nullptr;        // pinned
-    unsigned* h_counters = nullptr; // pinned: [0] changed splats (last propose)
-    SaLoopDev* h_loop = nullptr;    // pinned copy of the loop state
-    uint64_t n_changed = 0, n_proposed = 0;
-    int driver = 0;                 // 1: ggs_sa_propose/commit, 2: ggs_sa_run (not mixed)
-};
-
-void sa_free(SaSession* s) {
-    for (DevBuf* b : {&s->curr, &s->best, &s->nb, &s->nb_fits, &s->target, &s->mask, &s->draws,
-                      &s->cur_recs, &s->nb_recs, &s->nb_bnds, &s->cur_part, &s->nb_part, &s->dirty, &s->plan,
-                      &s->wpart, &s->order, &s->counters, &s->loop, &s->sit, &s->curves, &s->flags, &s->sizes,
-                      &s->fctr})
-        if (b->p) (void)hipFree(b->p);
-    if (s->h_loop) (void)hipHostFree(s->h_loop);
-    if (s->h_fits) (void)hipHostFree(s->h_fits);
-    if (s->h_counters) (void)hipHostFree(s->h_counters);
-    if (s->st) (void)hipStreamDestroy(s->st);
-}
-
-// prep -> [dirty] -> raster -> finalize for n genomes G; records / partials / fitness
-// land in recs / part / fits.  dirty != null: incremental against the current state.
-// bnds: the records' cull bounds (scratch for the current state's evaluation).
-int sa_eval(SaSession* s, const float* G, int n, SplatRec* recs, int4* bnds, float* part, float* fits, bool dirty,
-            bool have_recs = false) {
-    const ggs_ga_config& c = s->cfg;
-    if (!have_recs) {
-        ProfScope ps(s->st, 0);
-        GGS_HIP(launch_prep(s->st, true, G, (int64_t)n * s->N, 9, c.H, c.W, c.k_sigma, recs, bnds, nullptr,
-                            nullptr, nullptr));
-    }
-    if (dirty)
-        GGS_HIP(launch_dirty(s->st, (const float*)s->curr.p, G, (const SplatRec*)s->cur_recs.p, recs, n,
-                             s->N, c.H, c.W, (unsigned char*)s->dirty.p, (unsigned*)s->counters.p, nullptr,
-                             s->dirty_rule));
-    return raster_fitness(s->st, s->c->simds, recs, bnds, n, s->N, c.H, c.W, (const float4*)s->plan.p, part,
-                          (const float*)s->wpart.p, c.fitness_mode, (const int*)s->order.p, s->fctr, fits, false,
-                          dirty ? (const unsigned char*)s->dirty.p : nullptr, (const float*)s->cur_part.p);
-}
-
-// Shared validation of ggs_ga_create / ggs_sa_create.
-int ga_check_config(const ggs_ga_config& c, const float* mask_hw, bool sa) {
-    int rc = check_dims(c.pop_size, c.n_splats, 9, c.H, c.W);
+    const int rc = get_ctx(device, &c);
     if (rc) return rc;
-    if (c.pop_size < 1 || c.pop_size > ga_max_population())
-        return fail(GGS_EINVAL, "pop_size must be in [1, %d]", ga_max_population());
-    if (!sa && c.tour_k < 1) return fail(GGS_EINVAL, "tour_k must be >= 1");
-    if (!sa && c.elite_k > c.pop_size) return fail(GGS_EINVAL, "elite_k must be <= pop_size");
-    if (c.fitness_mode < GGS_FIT_NONE || c.fitness_mode > GGS_FIT_BOOST)
-        return fail(GGS_EINVAL, "bad fitness mode %d", c.fitness_mode);
-    if (c.fitness_mode != GGS_FIT_NONE && !mask_hw) return fail(GGS_EINVAL, "mode needs a mask");
-    return GGS_OK;
-}
-
-void ga_fill_log_bounds(ggs_ga_config* c) {   // utils.py:38-39 when the caller passed 0, 0
-    if (c->scale_log_lo == 0.0f && c->scale_log_hi == 0.0f) {
-        c->scale_log_lo = logf(c->min_scale_splats);
-        c->scale_log_hi = logf(c->max_scale_splats * (float)std::max(c->H, c->W));
-    }
-}
-
-void ga_free(GaSession* s) {
-    for (DevBuf* b : {&s->pop[0], &s->pop[1], &s->fits[0], &s->fits[1], &s->off[0], &s->off[1], &s->off_fits,
-                      &s->src, &s->elite[0], &s->elite[1],
-                      &s->target, &s->mask, &s->best_ind, &s->best_fit, &s->best_src, &s->best_upd,
-                      &s->curves, &s->draws, &s->recs, &s->bnds, &s->partials, &s->plan, &s->wpart, &s->order,
-                      &s->fctr})
-        if (b->p) (void)hipFree(b->p);
-    if (s->st) (void)hipStreamDestroy(s->st);
-}
-
-}  // namespace
-}  // namespace ggs
-
-extern "C" {
-
-int ggs_ga_create(int32_t device, const ggs_ga_config* cfg, const float* target_hw3,
-                  const float* mask_hw, const float* init_pop, void** handle) {
-    if (!cfg || !target_hw3 || !init_pop || !handle) return fail(GGS_EINVAL, "null argument");
-    const ggs_ga_config& c = *cfg;
-    int rc = ga_check_config(c, mask_hw, false);
-    if (rc) return rc;
-    DevCtx* ctx = nullptr;
-    if ((rc = get_ctx(device, &ctx))) return rc;
-    auto s = std::make_unique<GaSession>();
-    s->c = ctx;
-    s->cfg = c;
-    ga_fill_log_bounds(&s->cfg);
-    s->P = c.pop_size;
-    s->N = c.n_splats;
-    const size_t pb = sizeof(float) * 9 * (size_t)s->P * s->N, hw = (size_t)c.H * c.W;
-    // what every rank of a sharded session must agree on (ggs_ga_set_comm checks it)
-    s->fingerprint = hash_bytes(&s->cfg, sizeof s->cfg) * 0x9E3779B97F4A7C15ull ^
-                     hash_bytes(target_hw3, sizeof(float) * 3 * hw) * 0xC2B2AE3D27D4EB4Full ^
-                     (mask_hw ? hash_bytes(mask_hw, sizeof(float) * hw) : 0x165667B19E3779F9ull) ^
-                     rotl(hash_bytes(init_pop, pb), 29);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard dg(ctx->dev);
-    auto bail = [&](int code) { ga_free(s.get()); return code; };
-    if (hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess)
-        return bail(fail(GGS_EHIP, "stream creation failed"));
-    for (DevBuf* b : {&s->pop[0], &s->pop[1], &s->off[0], &s->off[1]})
-        if ((rc = ensure(*b, std::max<size_t>(pb, 4), s->st))) return bail(rc);
-    for (DevBuf* b : {&s->fits[0], &s->fits[1], &s->off_fits})
-        if ((rc = ensure(*b, sizeof(float) * s->P, s->st))) return bail(rc);
-    for (DevBuf* b : {&s->src, &s->elite[0], &s->elite[1]})
-        if ((rc = ensure(*b, sizeof(int) * s->P, s->st))) return bail(rc);
-    if ((rc = ensure(s->target, sizeof(float) * 3 * hw, s->st))) return bail(rc);
-    if (mask_hw && (rc = ensure(s->mask, sizeof(float) * hw, s->st))) return bail(rc);
-    if ((rc = ensure(s->best_ind, std::max<size_t>(sizeof(float) * 9 * s->N, 4), s->st))) return bail(rc);
-    if ((rc = ensure(s->best_fit, sizeof(double), s->st))) return bail(rc);
-    if ((rc = ensure(s->best_src, sizeof(int), s->st))) return bail(rc);
-    if ((rc = ensure(s->best_upd, sizeof(int), s->st))) return bail(rc);
-    int nTX;
-    s->nTiles = raster_tiles(c.H, c.W, &nTX);
-    const size_t slots = 4 * (size_t)s->nTiles;
-    if ((rc = ensure(s->recs, sizeof(SplatRec) * std::max<size_t>((size_t)s->P * s->N, 1), s->st)) ||
-        (rc = ensure(s->bnds, sizeof(int4) * std::max<size_t>((size_t)s->P * s->N, 1), s->st)) ||
-        (rc = ensure(s->partials, sizeof(float) * slots * s->P, s->st)) ||
-        (rc = ensure(s->plan, plan_bytes(c.H, c.W), s->st)) || (rc = ensure(s->wpart, plan_wsum_bytes(c.H, c.W), s->st)) ||
-        (rc = ensure(s->order, sizeof(int) * (size_t)raster_order_len(c.H, c.W), s->st)))
-        return bail(rc);
-    std::vector<int> order(raster_order_len(c.H, c.W));
-    raster_tile_order(c.H, c.W, order.data());
-    if (hipMemcpyAsync(s->target.p, target_hw3, sizeof(float) * 3 * hw, hipMemcpyHostToDevice, s->st) ||
-        (mask_hw && hipMemcpyAsync(s->mask.p, mask_hw, sizeof(float) * hw, hipMemcpyHostToDevice, s->st)) ||
-        hipMemcpyAsync(s->pop[0].p, init_pop, pb, hipMemcpyHostToDevice, s->st) ||
-        hipMemcpyAsync(s->order.p, order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice, s->st))
-        return bail(fail(GGS_EHIP, "upload failed"));
-    if (launch_plan(s->st, (const float*)s->target.p, mask_hw ? (const float*)s->mask.p : nullptr, c.fitness_mode,
-                    c.boost_beta, c.H, c.W, (float4*)s->plan.p, (float*)s->wpart.p) != hipSuccess)
-        return bail(fail(GGS_EHIP, "plan launch failed"));
-    if ((rc = run_fitness(ctx, s->st, (const float*)s->pop[0].p, s->P, s->N, 9, (const float*)s->target.p,
-                          mask_hw ? (const float*)s->mask.p : nullptr, c.fitness_mode, c.boost_beta,
-                          c.H, c.W, c.k_sigma, (float*)s->fits[0].p, s->plan_id)))
-        return bail(rc);
-    double* row;
-    if ((rc = ga_curves_row(s.get(), &row))) return bail(rc);
-    if (launch_ga_survivors(s->st, (const float*)s->fits[0].p, nullptr, s->P, c.elite_k, (int*)s->src.p,
-                            nullptr, ga_best(s.get()), row, 1, FitReduce{}, (int*)s->elite[0].p) ||
-        launch_ga_gather(s->st, (const float*)s->pop[0].p, nullptr, s->P, s->N, nullptr, nullptr,
-                         ga_best(s.get()), 1))
-        return bail(fail(GGS_EHIP, "init launch failed"));
-    if (hipStreamSynchronize(s->st) != hipSuccess)     // init_pop / target may be freed on return
-        return bail(fail(GGS_EHIP, "initial evaluation failed"));
-    s->n_curves = 1;
-    *handle = s.release();
-    return GGS_OK;
-}
-
-int ggs_ga_set_comm(void* handle, void* comm) {
-    GaSession* s = (GaSession*)handle;
-    if (!s) return fail(GGS_EINVAL, "null GA handle");
-    int32_t n = 1, r = 0;
-    if (comm) {
-        int rc = ggs_comm_size(comm, &n, &r);
-        if (rc) return rc;
-        // the ranks must breed identical offspring: compare the sessions' fingerprints
-        // (exchanged as two float32 bit patterns; an all-gather only moves bytes)
-        float mine[2];
-        memcpy(mine, &s->fingerprint, sizeof mine);
-        std::vector<float> all(2 * (size_t)n);
-        if ((rc = ggs_comm_allgather_host(comm, mine, all.data(), 2))) return rc;
-        for (int k = 0; k < n; ++k) {
-            uint64_t f;
-            memcpy(&f, &all[2 * (size_t)k], sizeof f);
-            if (f != s->fingerprint)
-                return fail(GGS_EINVAL, "ggs_ga_set_comm: rank %d's session differs from rank %d's (config, "
-                            "target, mask, initial population or seed): the shards would mix populations",
-                            k, r);
-        }
-    }
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    const int per = (s->P + n - 1) / n;
-    int rc = ensure(s->off_fits, sizeof(float) * (size_t)per * n, s->st);   // gather target: n shards
-    if (rc) return rc;
-    s->comm = comm;
-    s->nranks = n;
-    s->rank = r;
-    return GGS_OK;
-}
-
-int ggs_ga_step(void* handle, int32_t gen, int32_t total_gens, const ggs_ga_draws* draws) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    GaSession* s = (GaSession*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    const int rc = ga_generation(s, gen, total_gens, draws);
-    if (rc || !draws) return rc;
-    GGS_HIP(hipStreamSynchronize(s->st));   // the caller's draw arrays are released on return
-    return GGS_OK;
-}
-
-int ggs_ga_run(void* handle, int32_t first_gen, int32_t n_gens, int32_t total_gens) {
-    if (!handle || n_gens < 0) return fail(GGS_EINVAL, "bad arguments");
-    GaSession* s = (GaSession*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    for (int g = 0; g < n_gens; ++g) {
-        const int rc = ga_generation(s, first_gen + g, total_gens, nullptr);
-        if (rc) return rc;
-    }
-    return GGS_OK;
-}
-
-int ggs_ga_read(void* handle, float* pop, float* fits, float* best_ind, double* best_fit,
-                double* curves, int32_t* n_curves) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    GaSession* s = (GaSession*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    const int rc = ga_flush(s);   // the last generation's survivors
-    if (rc) return rc;
-    GGS_HIP(hipStreamSynchronize(s->st));
-    if (pop) GGS_HIP(hipMemcpy(pop, s->pop[s->cur].p, sizeof(float) * 9 * (size_t)s->P * s->N, hipMemcpyDeviceToHost));
-    if (fits) GGS_HIP(hipMemcpy(fits, s->fits[s->cur].p, sizeof(float) * s->P, hipMemcpyDeviceToHost));
-    if (best_ind) GGS_HIP(hipMemcpy(best_ind, s->best_ind.p, sizeof(float) * 9 * (size_t)s->N, hipMemcpyDeviceToHost));
-    if (best_fit) GGS_HIP(hipMemcpy(best_fit, s->best_fit.p, sizeof(double), hipMemcpyDeviceToHost));
-    if (curves) GGS_HIP(hipMemcpy(curves, s->curves.p, sizeof(double) * 3 * s->n_curves, hipMemcpyDeviceToHost));
-    if (n_curves) *n_curves = (int32_t)s->n_curves;
-    return GGS_OK;
-}
-
-void ggs_ga_destroy(void* handle) {
-    if (!handle) return;
-    GaSession* s = (GaSession*)handle;
-    {
-        std::lock_guard<std::mutex> lk(s->c->mu);
-        DeviceGuard dg(s->c->dev);
-        if (s->st) (void)hipStreamSynchronize(s->st);
-        ga_free(s);
-    }
-    delete s;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return (int)c->ws.size();
 }
 
 }  // extern "C"
 
-// ---- Adam refiner: what the refine sessions and the island group's polish share ----
+// ---- what the session units share (ggs_host.h) --------------------------------------
 namespace ggs {
-namespace {
-int refine_check_params(const ggs_refine_params* p) {
-    if (!p) return fail(GGS_EINVAL, "null ggs_refine_params");
-    for (int c = 0; c < 9; ++c)
-        if (!std::isfinite(p->lr[c]) || p->lr[c] < 0.0f) return fail(GGS_EINVAL, "lr[%d]=%g must be finite and >= 0", c, p->lr[c]);
-    if (!(p->beta1 >= 0.0f && p->beta1 < 1.0f)) return fail(GGS_EINVAL, "beta1=%g must be in [0, 1)", p->beta1);
-    if (!(p->beta2 >= 0.0f && p->beta2 < 1.0f)) return fail(GGS_EINVAL, "beta2=%g must be in [0, 1)", p->beta2);
-    if (!(p->eps > 0.0f) || !std::isfinite(p->eps)) return fail(GGS_EINVAL, "eps=%g must be > 0", p->eps);
-    return GGS_OK;
-}
 
-// step t's constants (t from 1); cfg: the scale bounds, filled (ga_fill_log_bounds)
-RefineStepDev refine_step_dev(const ggs_refine_params& prm, const ggs_ga_config& cfg, int64_t t) {
-    RefineStepDev p;
-    for (int c = 0; c < 9; ++c) p.lr[c] = prm.lr[c];
-    p.beta1 = prm.beta1;
-    p.beta2 = prm.beta2;
-    p.eps = prm.eps;
-    p.c1 = (float)(1.0 - pow((double)prm.beta1, (double)t));
-    p.c2 = (float)(1.0 - pow((double)prm.beta2, (double)t));
-    p.log_lo = cfg.scale_log_lo;
-    p.log_hi = cfg.scale_log_hi;
-    return p;
-}
-
-// A session's stream is about to be destroyed: the context's pipeline workspace of
-// that stream goes with it (a later stream may get the same handle).
 void release_workspace(DevCtx* c, hipStream_t st) {
     for (auto it = c->ws.begin(); it != c->ws.end(); ++it)
         if ((*it)->stream == st) {
-            Workspace* w = it->get();
-            for (DevBuf* b : {&w->recs, &w->bnds, &w->partials, &w->wpartials, &w->order, &w->plan, &w->fctr,
-                              &w->maskws, &w->swords, &w->smasks, &w->gf9, &w->gi4, &w->gpart, &w->gout,
-                              &w->lpart, &w->limg, &w->lcot})
-                if (b->p) (void)hipFree(b->p);
             c->ws.erase(it);
             return;
         }
 }
 
-// The pipeline buffers a gradient call over B candidates takes from the stream's
-// workspace, made now so that no later call allocates.
+uint64_t new_plan_key() {
+    static std::atomic<uint64_t> g_session_ids{0};
+    return (1ull << 63) | ++g_session_ids;
+}
+
+int Session::open(const float* target_host, const float* mask_host, int n_images, int n_plans, bool raster) {
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
+        st = nullptr;
+        return fail(GGS_EHIP, "stream creation failed");
+    }
+    const int H = cfg.H, W = cfg.W;
+    const size_t hw = (size_t)n_images * H * W;
+    int rc;
+    if ((rc = ensure(target, sizeof(float) * 3 * hw, st)) ||
+        (mask_host && (rc = ensure(mask, sizeof(float) * hw, st))) ||
+        (n_plans && ((rc = ensure(plan, (size_t)n_plans * plan_bytes(H, W), st)) ||
+                     (rc = ensure(wpart, (size_t)n_plans * plan_wsum_bytes(H, W), st)))) ||
+        (raster && (rc = ensure(order, sizeof(int) * (size_t)raster_order_len(H, W), st))))
+        return rc;
+    if (hipMemcpyAsync(target.p, target_host, sizeof(float) * 3 * hw, hipMemcpyHostToDevice, st) ||
+        (mask_host && hipMemcpyAsync(mask.p, mask_host, sizeof(float) * hw, hipMemcpyHostToDevice, st)))
+        return fail(GGS_EHIP, "upload failed");
+    if (raster) {
+        order_host.resize(raster_order_len(H, W));
+        raster_tile_order(H, W, order_host.data());
+        if (hipMemcpyAsync(order.p, order_host.data(), sizeof(int) * order_host.size(), hipMemcpyHostToDevice, st))
+            return fail(GGS_EHIP, "upload failed");
+    }
+    if (n_plans && launch_plan_set(st, (const float*)target.p, d_mask(), cfg.fitness_mode, cfg.boost_beta, H, W,
+                                   n_plans, (float4*)plan.p, (float*)wpart.p) != hipSuccess)
+        return fail(GGS_EHIP, "plan launch failed");
+    return GGS_OK;
+}
+
 int reserve_grad_workspace(DevCtx* c, hipStream_t st, int64_t B, int N, int H, int W) {
     Workspace* w = workspace_for(c, st);
     int nTX;
@@ -2239,1701 +1662,5 @@ int reserve_grad_workspace(DevCtx* c, hipStream_t st, int64_t B, int N, int H, i
         return rc;
     return GGS_OK;
 }
-}  // namespace
+
 }  // namespace ggs
-
-// ---- island groups (ggs_ga_islands_*) -------------------------------------------
-namespace ggs {
-namespace {
-
-// K populations of P rows in one session: every per-population array of GaSession
-// with a leading island dimension, one stream / plan / tile order / counter block.
-// The evaluated offspring are compact: island k's offspring o < Pe = P - E is
-// candidate k * Pe + o of the generation's one raster launch (recs, bnds,
-// partials, off_fits).  curves: [generation][K][3] on the device.
-struct GaIslands {
-    uint64_t plan_id = new_plan_id();
-    DevCtx* c = nullptr;
-    hipStream_t st = nullptr;
-    ggs_ga_config cfg{};
-    int K = 0, P = 0, N = 0, Pe = 0, cur = 0, ocur = 0;
-    int migrate_every = 0, n_migrants = 0;
-    bool pending = false;          // the last generation's survivors / gather not applied yet
-    int pending_gen = 0;           // ... and which generation that is (migrations count absolutely)
-    DevBuf pop[2], fits[2], off[2], elite[2], off_fits, src, target, mask, best_ind, best_fit, best_src,
-        best_upd, curves, seeds, mig;
-    DevBuf recs, bnds, partials, plan, wpart, order, fctr;
-    int64_t n_curves = 0, curves_cap = 0;
-    // a target per island (ggs_ga_islands_create_targets): target [K][H][W][3], mask
-    // [K][H][W], plan / wpart a plan set of K; island k's candidates are scored
-    // against plan k, and a migration re-scores the immigrants (mig_gen [K][m][N][9],
-    // their genomes staged compactly; mig_fits [K][m])
-    bool multi = false;
-    DevBuf mig_gen, mig_fits;
-    // memetic generations (ggs_ga_islands_set_polish; every or n_steps 0: off): island
-    // k's n_rows best-ranked rows are refine candidates k * n_rows + j
-    ggs_ga_polish polish{};
-    DevBuf px, pm, pv, pgrad, pbest_x, pbest_fit, pfits, prows;
-};
-
-void gi_free(GaIslands* s) {
-    for (DevBuf* b : {&s->pop[0], &s->pop[1], &s->fits[0], &s->fits[1], &s->off[0], &s->off[1], &s->elite[0],
-                      &s->elite[1], &s->off_fits, &s->src, &s->target, &s->mask, &s->best_ind, &s->best_fit,
-                      &s->best_src, &s->best_upd, &s->curves, &s->seeds, &s->mig, &s->recs, &s->bnds,
-                      &s->partials, &s->plan, &s->wpart, &s->order, &s->fctr, &s->mig_gen, &s->mig_fits, &s->px,
-                      &s->pm, &s->pv, &s->pgrad, &s->pbest_x, &s->pbest_fit, &s->pfits, &s->prows})
-        if (b->p) (void)hipFree(b->p);
-    if (s->st) {
-        // the initial evaluation and the polish run through the stream's workspace
-        release_workspace(s->c, s->st);
-        (void)hipStreamDestroy(s->st);
-    }
-}
-
-GaBestDev gi_best(GaIslands* s) {
-    return {(double*)s->best_fit.p, (int*)s->best_src.p, (int*)s->best_upd.p, (float*)s->best_ind.p};
-}
-
-int gi_curves_row(GaIslands* s, double** row) {
-    const size_t rb = sizeof(double) * 3 * (size_t)s->K;      // one generation: [K][3]
-    if (s->n_curves >= s->curves_cap) {
-        const int64_t cap = std::max<int64_t>(64, s->curves_cap * 2);
-        DevBuf nb;
-        GGS_HIP(hipMalloc(&nb.p, rb * cap));
-        nb.cap = rb * cap;
-        if (s->curves.p) {
-            const hipError_t e = hipMemcpyAsync(nb.p, s->curves.p, rb * s->n_curves, hipMemcpyDeviceToDevice, s->st);
-            if (e != hipSuccess || hipStreamSynchronize(s->st) != hipSuccess) {
-                (void)hipFree(nb.p);
-                return fail(GGS_EHIP, "curves copy failed");
-            }
-            GGS_HIP(hipFree(s->curves.p));
-        }
-        s->curves = nb;
-        s->curves_cap = cap;
-    }
-    *row = (double*)s->curves.p + 3 * (int64_t)s->K * s->n_curves;
-    return GGS_OK;
-}
-
-bool gi_migrates(const GaIslands* s, int gen) {
-    return s->K >= 2 && s->migrate_every > 0 && s->n_migrants > 0 && gen % s->migrate_every == 0;
-}
-
-bool gi_fused() {
-    static const bool off = getenv("GGS_GA_UNFUSED") && atoi(getenv("GGS_GA_UNFUSED")) != 0;
-    return !off;
-}
-
-bool gi_polishes(const GaIslands* s, int gen) {
-    return s->polish.every > 0 && s->polish.n_steps > 0 && gen % s->polish.every == 0;
-}
-
-// One polish of every island, all on the session's stream: the ranked rows staged
-// as K * n_rows refine candidates (zero moments, t from 1), n_steps steps as
-// ggs_refine_run takes them and ggs_refine_read's closing evaluation, each one
-// chain of launches for all candidates against their island's image, then the
-// install (strictly lower only), the elite lists and the best so far.
-int gi_polish(GaIslands* s) {
-    const ggs_ga_config& c = s->cfg;
-    const int R = s->polish.n_rows, B = s->K * R, N = s->N, cur = s->cur;
-    const size_t pb = sizeof(float) * 9 * (size_t)B * N;
-    const float* d_mask = s->mask.p ? (const float*)s->mask.p : nullptr;
-    const int group = s->multi ? R : 0;     // a shared target: the one plan, ggs_refine_create's path
-    int rc;
-    GGS_HIP(launch_polish_stage(s->st, s->K, (const float*)s->pop[cur].p, (const float*)s->fits[cur].p, s->P, N, R,
-                                (int*)s->prows.p, (float*)s->px.p, (float*)s->pbest_x.p, (double*)s->pbest_fit.p));
-    GGS_HIP(hipMemsetAsync(s->pm.p, 0, pb, s->st));
-    GGS_HIP(hipMemsetAsync(s->pv.p, 0, pb, s->st));
-    for (int t = 1; t <= s->polish.n_steps; ++t) {
-        if ((rc = run_fitness_grad_planned(s->c, s->st, (const float*)s->px.p, B, N, 9, (const float4*)s->plan.p,
-                                           (const float*)s->wpart.p, (const float*)s->target.p, d_mask,
-                                           c.fitness_mode, c.boost_beta, c.H, c.W, group, c.k_sigma,
-                                           (float*)s->pfits.p, (float*)s->pgrad.p)))
-            return rc;
-        GGS_HIP(launch_refine_best(s->st, (const float*)s->px.p, (const float*)s->pfits.p, B, N,
-                                   (double*)s->pbest_fit.p, (float*)s->pbest_x.p));
-        GGS_HIP(launch_refine_adam(s->st, (float*)s->px.p, (float*)s->pm.p, (float*)s->pv.p, (const float*)s->pgrad.p,
-                                   B, N, refine_step_dev(s->polish.adam, c, t)));
-    }
-    if ((rc = run_fitness_planned(s->c, s->st, (const float*)s->px.p, B, N, 9, (const float4*)s->plan.p,
-                                  (const float*)s->wpart.p, c.fitness_mode, c.H, c.W, c.k_sigma, (float*)s->pfits.p,
-                                  group)))
-        return rc;
-    GGS_HIP(launch_refine_best(s->st, (const float*)s->px.p, (const float*)s->pfits.p, B, N, (double*)s->pbest_fit.p,
-                               (float*)s->pbest_x.p));
-    GGS_HIP(launch_polish_install(s->st, s->K, (float*)s->pop[cur].p, (float*)s->fits[cur].p, s->P, N, R, c.elite_k,
-                                  (const int*)s->prows.p, (const float*)s->pbest_x.p, (const double*)s->pbest_fit.p,
-                                  (int*)s->elite[cur].p, (double*)s->best_fit.p, (float*)s->best_ind.p));
-    return GGS_OK;
-}
-
-// ga_flush for the group, then the pending generation's migration and polish if they are due.
-int gi_flush(GaIslands* s) {
-    if (!s->pending) return GGS_OK;
-    const int nxt = 1 - s->cur;
-    double* row;
-    int rc;
-    if ((rc = gi_curves_row(s, &row))) return rc;
-    GGS_HIP(launch_ga_survivors_islands(s->st, s->K, (const float*)s->fits[s->cur].p, (const float*)s->off_fits.p,
-                                        s->P, s->N, s->cfg.elite_k, (int*)s->src.p, (float*)s->fits[nxt].p,
-                                        gi_best(s), row, 0, (int*)s->elite[nxt].p));
-    GGS_HIP(launch_ga_gather_islands(s->st, s->K, (const float*)s->pop[s->cur].p, (const float*)s->off[s->ocur].p,
-                                     s->P, s->N, s->cfg.elite_k, (const int*)s->src.p, (float*)s->pop[nxt].p,
-                                     gi_best(s), 0));
-    s->cur = nxt;
-    s->n_curves += 1;
-    s->pending = false;
-    if (gi_migrates(s, s->pending_gen) && !s->multi)
-        GGS_HIP(launch_ga_migrate(s->st, s->K, (float*)s->pop[nxt].p, (float*)s->fits[nxt].p, s->P, s->N,
-                                  s->n_migrants, s->cfg.elite_k, (int*)s->mig.p, (int*)s->elite[nxt].p));
-    else if (gi_migrates(s, s->pending_gen)) {
-        // A target per island: an immigrant's fitness was measured against its source
-        // island's target, so the genomes move first, the K * m immigrants are scored
-        // against their new island's plan (one prep + one grouped raster, group m; the
-        // generation's records and partials are free by now), and only then are the
-        // fitness rows installed and the elites re-ranked.
-        const int m = s->n_migrants, Bm = s->K * m;
-        const ggs_ga_config& c = s->cfg;
-        GGS_HIP(launch_ga_migrate_copy(s->st, s->K, (float*)s->pop[nxt].p, (const float*)s->fits[nxt].p, s->P, s->N,
-                                       m, (int*)s->mig.p, (float*)s->mig_gen.p));
-        {
-            ProfScope ps(s->st, 0);
-            GGS_HIP(launch_prep(s->st, true, (const float*)s->mig_gen.p, (int64_t)Bm * s->N, 9, c.H, c.W, c.k_sigma,
-                                (SplatRec*)s->recs.p, (int4*)s->bnds.p, nullptr, nullptr, nullptr));
-        }
-        if ((rc = raster_fitness(s->st, s->c->simds, (const SplatRec*)s->recs.p, (const int4*)s->bnds.p, Bm, s->N,
-                                 c.H, c.W, (const float4*)s->plan.p, (float*)s->partials.p, (const float*)s->wpart.p,
-                                 c.fitness_mode, (const int*)s->order.p, s->fctr, (float*)s->mig_fits.p, true,
-                                 nullptr, nullptr, m)))
-            return rc;
-        GGS_HIP(launch_ga_migrate_install(s->st, s->K, (float*)s->fits[nxt].p, s->P, m, c.elite_k,
-                                          (const int*)s->mig.p, (const float*)s->mig_fits.p, (int*)s->elite[nxt].p));
-    }
-    if (gi_polishes(s, s->pending_gen) && (rc = gi_polish(s))) return rc;
-    return GGS_OK;
-}
-
-int gi_generation(GaIslands* s, int gen, int total) {
-    const int K = s->K, P = s->P, N = s->N;
-    const ggs_ga_config& c = s->cfg;
-    const GaParamsDev prm = ga_params(c, gen, total);
-    const int onew = 1 - s->ocur;
-    int rc;
-    // a generation whose survivors are followed by a migration or a polish is closed
-    // unfused (flush, migrate, polish); the plain variation launch then breeds from pop / fits
-    if (s->pending && gi_fused() && !gi_migrates(s, s->pending_gen) && !gi_polishes(s, s->pending_gen)) {
-        const int nxt = 1 - s->cur;
-        double* row;
-        if ((rc = gi_curves_row(s, &row))) return rc;
-        BreedDev br{(const float*)s->pop[s->cur].p, (const float*)s->fits[s->cur].p,
-                    (const float*)s->off[s->ocur].p, (const float*)s->off_fits.p,
-                    (const int*)s->elite[s->cur].p, (int*)s->elite[nxt].p, (float*)s->pop[nxt].p,
-                    (float*)s->fits[nxt].p, row, gi_best(s), c.elite_k};
-        {
-            ProfScope ps(s->st, 0);
-            GGS_HIP(launch_ga_variation_islands(s->st, K, nullptr, nullptr, P, N, prm, (const uint64_t*)s->seeds.p,
-                                                gen, (float*)s->off[onew].p, (SplatRec*)s->recs.p,
-                                                (int4*)s->bnds.p, c.H, c.W, c.k_sigma, c.elite_k, &br));
-        }
-        s->cur = nxt;
-        s->n_curves += 1;
-    } else {
-        if ((rc = gi_flush(s))) return rc;
-        ProfScope ps(s->st, 0);
-        GGS_HIP(launch_ga_variation_islands(s->st, K, (const float*)s->pop[s->cur].p,
-                                            (const float*)s->fits[s->cur].p, P, N, prm,
-                                            (const uint64_t*)s->seeds.p, gen, (float*)s->off[onew].p,
-                                            (SplatRec*)s->recs.p, (int4*)s->bnds.p, c.H, c.W, c.k_sigma, c.elite_k));
-    }
-    s->ocur = onew;
-    s->pending = true;
-    s->pending_gen = gen;
-    const int B = K * s->Pe;        // one contiguous batch: island k's offspring o at k * Pe + o
-    if (B > 0 && (rc = raster_fitness(s->st, s->c->simds, (const SplatRec*)s->recs.p, (const int4*)s->bnds.p, B, N,
-                                      c.H, c.W, (const float4*)s->plan.p, (float*)s->partials.p,
-                                      (const float*)s->wpart.p, c.fitness_mode, (const int*)s->order.p, s->fctr,
-                                      (float*)s->off_fits.p, true, nullptr, nullptr, s->multi ? s->Pe : 0)))
-        return rc;
-    return GGS_OK;
-}
-
-int gi_check(const ggs_ga_config* cfg, const ggs_ga_islands* isl, const float* target_hw3, const float* mask_hw,
-             const float* init_pops, void** handle) {
-    if (!cfg || !isl || !target_hw3 || !handle) return fail(GGS_EINVAL, "null argument");
-    int rc = ga_check_config(*cfg, mask_hw, false);
-    if (rc) return rc;
-    if (isl->n_islands < 1 || isl->n_islands > 65535)
-        return fail(GGS_EINVAL, "n_islands must be in [1, 65535], got %d", isl->n_islands);
-    if (cfg->pop_size > ga_breed_max_population())
-        return fail(GGS_EINVAL, "an island's pop_size must be <= %d, got %d", ga_breed_max_population(),
-                    cfg->pop_size);
-    if (isl->migrate_every < 0) return fail(GGS_EINVAL, "migrate_every must be >= 0, got %d", isl->migrate_every);
-    if (isl->n_migrants < 0 || isl->n_migrants > cfg->pop_size / 2)
-        return fail(GGS_EINVAL, "n_migrants must be in [0, pop_size / 2 = %d], got %d", cfg->pop_size / 2,
-                    isl->n_migrants);
-    if (isl->topology != 0) return fail(GGS_EINVAL, "topology %d: only 0 (ring) exists", isl->topology);
-    if (!isl->seeds) return fail(GGS_EINVAL, "seeds is required ([n_islands])");
-    if (!init_pops) return fail(GGS_EINVAL, "init_pops is required ([K, P, N, 9])");
-    return check_dims((int64_t)isl->n_islands * cfg->pop_size, cfg->n_splats, 9, cfg->H, cfg->W);
-}
-
-// ggs_ga_islands_create (multi false: target_hw3 [H][W][3], mask_hw [H][W] shared by
-// the islands) and ggs_ga_islands_create_targets (multi: [K][H][W][3], [K][H][W]).
-int gi_create(int32_t device, const ggs_ga_config* cfg, const ggs_ga_islands* isl, const float* target_hw3,
-              const float* mask_hw, const float* init_pops, void** handle, bool multi) {
-    int rc = gi_check(cfg, isl, target_hw3, mask_hw, init_pops, handle);   // before any device call
-    if (rc) return rc;
-    const ggs_ga_config& c = *cfg;
-    DevCtx* ctx = nullptr;
-    if ((rc = get_ctx(device, &ctx))) return rc;
-    auto s = std::make_unique<GaIslands>();
-    s->c = ctx;
-    s->cfg = c;
-    ga_fill_log_bounds(&s->cfg);
-    const int K = s->K = isl->n_islands, P = s->P = c.pop_size, N = s->N = c.n_splats;
-    s->Pe = P - (c.elite_k < 1 ? 1 : c.elite_k);
-    s->migrate_every = isl->migrate_every;
-    s->n_migrants = isl->n_migrants;
-    s->multi = multi;
-    const size_t nplans = multi ? (size_t)K : 1;
-    const size_t KP = (size_t)K * P;
-    // the raster batch: the generation's K * Pe offspring, or a migration's K * m immigrants
-    const size_t Bm = multi && K >= 2 && s->migrate_every > 0 ? (size_t)K * s->n_migrants : 0;
-    const size_t B = std::max((size_t)K * s->Pe, Bm);
-    const size_t pb = sizeof(float) * 9 * KP * N, hw = nplans * (size_t)c.H * c.W;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard dg(ctx->dev);
-    // error returns: sync what was enqueued (the caller's arrays may be freed on return), free everything
-    auto bail = [&](int code) {
-        const std::string keep = t_err;
-        if (s->st) (void)hipStreamSynchronize(s->st);
-        gi_free(s.get());
-        t_err = keep;
-        return code;
-    };
-    if (hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess)
-        return bail(fail(GGS_EHIP, "stream creation failed"));
-    for (DevBuf* b : {&s->pop[0], &s->pop[1], &s->off[0], &s->off[1]})
-        if ((rc = ensure(*b, std::max<size_t>(pb, 4), s->st))) return bail(rc);
-    for (DevBuf* b : {&s->fits[0], &s->fits[1]})
-        if ((rc = ensure(*b, sizeof(float) * KP, s->st))) return bail(rc);
-    if ((rc = ensure(s->off_fits, sizeof(float) * std::max<size_t>(B, 1), s->st))) return bail(rc);
-    for (DevBuf* b : {&s->src, &s->elite[0], &s->elite[1]})
-        if ((rc = ensure(*b, sizeof(int) * KP, s->st))) return bail(rc);
-    // migration scratch: row lists, zeroed so that an entry is a valid row whatever the fitness values
-    if ((rc = ensure_zeroed(s->mig, sizeof(int) * 2 * (size_t)std::max(s->n_migrants, 1) * K, s->st)))
-        return bail(rc);
-    if ((rc = ensure(s->target, sizeof(float) * 3 * hw, s->st))) return bail(rc);
-    if (mask_hw && (rc = ensure(s->mask, sizeof(float) * hw, s->st))) return bail(rc);
-    if ((rc = ensure(s->best_ind, std::max<size_t>(sizeof(float) * 9 * (size_t)K * N, 4), s->st))) return bail(rc);
-    if ((rc = ensure(s->best_fit, sizeof(double) * K, s->st))) return bail(rc);
-    if ((rc = ensure(s->best_src, sizeof(int) * K, s->st))) return bail(rc);
-    if ((rc = ensure(s->best_upd, sizeof(int) * K, s->st))) return bail(rc);
-    if ((rc = ensure(s->seeds, sizeof(uint64_t) * K, s->st))) return bail(rc);
-    if (Bm && ((rc = ensure(s->mig_gen, std::max<size_t>(sizeof(float) * 9 * Bm * N, 4), s->st)) ||
-               (rc = ensure(s->mig_fits, sizeof(float) * Bm, s->st))))
-        return bail(rc);
-    int nTX;
-    const size_t slots = 4 * (size_t)raster_tiles(c.H, c.W, &nTX);
-    if ((rc = ensure(s->recs, sizeof(SplatRec) * std::max<size_t>(B * N, 1), s->st)) ||
-        (rc = ensure(s->bnds, sizeof(int4) * std::max<size_t>(B * N, 1), s->st)) ||
-        (rc = ensure(s->partials, sizeof(float) * slots * std::max<size_t>(B, 1), s->st)) ||
-        (rc = ensure(s->plan, nplans * plan_bytes(c.H, c.W), s->st)) ||
-        (rc = ensure(s->wpart, nplans * plan_wsum_bytes(c.H, c.W), s->st)) ||
-        (rc = ensure(s->order, sizeof(int) * (size_t)raster_order_len(c.H, c.W), s->st)))
-        return bail(rc);
-    std::vector<int> order(raster_order_len(c.H, c.W));
-    raster_tile_order(c.H, c.W, order.data());
-    if (hipMemcpyAsync(s->target.p, target_hw3, sizeof(float) * 3 * hw, hipMemcpyHostToDevice, s->st) ||
-        (mask_hw && hipMemcpyAsync(s->mask.p, mask_hw, sizeof(float) * hw, hipMemcpyHostToDevice, s->st)) ||
-        hipMemcpyAsync(s->pop[0].p, init_pops, pb, hipMemcpyHostToDevice, s->st) ||
-        hipMemcpyAsync(s->seeds.p, isl->seeds, sizeof(uint64_t) * K, hipMemcpyHostToDevice, s->st) ||
-        hipMemcpyAsync(s->order.p, order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice, s->st))
-        return bail(fail(GGS_EHIP, "upload failed"));
-    if (launch_plan_set(s->st, (const float*)s->target.p, mask_hw ? (const float*)s->mask.p : nullptr,
-                        c.fitness_mode, c.boost_beta, c.H, c.W, (int)nplans, (float4*)s->plan.p,
-                        (float*)s->wpart.p) != hipSuccess)
-        return bail(fail(GGS_EHIP, "plan launch failed"));
-    if (multi) {    // the initial [K][P] population, island k's rows against plan k
-        if ((rc = run_fitness_planned(ctx, s->st, (const float*)s->pop[0].p, (int64_t)KP, N, 9,
-                                      (const float4*)s->plan.p, (const float*)s->wpart.p, c.fitness_mode, c.H, c.W,
-                                      c.k_sigma, (float*)s->fits[0].p, P)))
-            return bail(rc);
-    } else if ((rc = run_fitness(ctx, s->st, (const float*)s->pop[0].p, (int64_t)KP, N, 9, (const float*)s->target.p,
-                                 mask_hw ? (const float*)s->mask.p : nullptr, c.fitness_mode, c.boost_beta,
-                                 c.H, c.W, c.k_sigma, (float*)s->fits[0].p, s->plan_id)))
-        return bail(rc);
-    double* row;
-    if ((rc = gi_curves_row(s.get(), &row))) return bail(rc);
-    if (launch_ga_survivors_islands(s->st, K, (const float*)s->fits[0].p, nullptr, P, N, c.elite_k, (int*)s->src.p,
-                                    nullptr, gi_best(s.get()), row, 1, (int*)s->elite[0].p) ||
-        launch_ga_gather_islands(s->st, K, (const float*)s->pop[0].p, nullptr, P, N, c.elite_k, nullptr, nullptr,
-                                 gi_best(s.get()), 1))
-        return bail(fail(GGS_EHIP, "init launch failed"));
-    if (hipStreamSynchronize(s->st) != hipSuccess)     // init_pops / target / seeds may be freed on return
-        return bail(fail(GGS_EHIP, "initial evaluation failed"));
-    s->n_curves = 1;
-    *handle = s.release();
-    return GGS_OK;
-}
-}  // namespace
-}  // namespace ggs
-extern "C" {
-
-int ggs_ga_islands_create(int32_t device, const ggs_ga_config* cfg, const ggs_ga_islands* isl,
-                          const float* target_hw3, const float* mask_hw, const float* init_pops, void** handle) {
-    return ggs::gi_create(device, cfg, isl, target_hw3, mask_hw, init_pops, handle, false);
-}
-
-int ggs_ga_islands_create_targets(int32_t device, const ggs_ga_config* cfg, const ggs_ga_islands* isl,
-                                  const float* targets_khw3, const float* masks_khw, const float* init_pops,
-                                  void** handle) {
-    return ggs::gi_create(device, cfg, isl, targets_khw3, masks_khw, init_pops, handle, true);
-}
-
-int ggs_ga_islands_run(void* handle, int32_t first_gen, int32_t n_gens, int32_t total_gens) {
-    if (!handle || n_gens < 0) return fail(GGS_EINVAL, "bad arguments");
-    GaIslands* s = (GaIslands*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    for (int g = 0; g < n_gens; ++g) {
-        const int rc = gi_generation(s, first_gen + g, total_gens);
-        if (rc) return rc;
-    }
-    return GGS_OK;
-}
-
-int ggs_ga_islands_set_polish(void* handle, const ggs_ga_polish* polish) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    GaIslands* s = (GaIslands*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    if (!polish) {
-        DeviceGuard dg(s->c->dev);
-        const int rc = gi_flush(s);     // a generation already run is closed under the setting it ran with
-        if (rc) return rc;
-        s->polish = ggs_ga_polish{};
-        return GGS_OK;
-    }
-    const ggs_ga_polish& q = *polish;
-    const int Emax = std::max(1, s->cfg.elite_k);
-    if (q.every < 0 || q.n_steps < 0) return fail(GGS_EINVAL, "every=%d and n_steps=%d must be >= 0", q.every, q.n_steps);
-    if (q.n_rows < 1 || q.n_rows > Emax)
-        return fail(GGS_EINVAL, "n_rows must be in [1, max(1, elite_k) = %d], got %d", Emax, q.n_rows);
-    int rc = refine_check_params(&q.adam);
-    if (rc) return rc;
-    if (s->P > polish_max_population())
-        return fail(GGS_EINVAL, "an island's pop_size must be <= %d, got %d", polish_max_population(), s->P);
-    const ggs_ga_config& c = s->cfg;
-    const int64_t B = (int64_t)s->K * q.n_rows;
-    // the candidates' batch limits and the partial budget (GGS_ENOMEM)
-    if ((rc = check_grad_dims(B, s->N, 9, c.H, c.W, c.fitness_mode, s->mask.p))) return rc;
-    DeviceGuard dg(s->c->dev);
-    const size_t pb = sizeof(float) * 9 * (size_t)B * s->N;
-    if ((rc = ensure(s->px, pb, s->st)) || (rc = ensure(s->pm, pb, s->st)) || (rc = ensure(s->pv, pb, s->st)) ||
-        (rc = ensure(s->pgrad, pb, s->st)) || (rc = ensure(s->pbest_x, pb, s->st)) ||
-        (rc = ensure(s->pbest_fit, sizeof(double) * (size_t)B, s->st)) ||
-        (rc = ensure(s->pfits, sizeof(float) * (size_t)B, s->st)) ||
-        (rc = ensure(s->prows, sizeof(int) * (size_t)B, s->st)) ||
-        (rc = reserve_grad_workspace(s->c, s->st, B, s->N, c.H, c.W)))
-        return rc;              // buffers only grew: the session's settings are as they were
-    if ((rc = gi_flush(s))) return rc;  // a generation already run is closed under the setting it ran with
-    s->polish = q;
-    return GGS_OK;
-}
-
-int ggs_ga_islands_read(void* handle, float* pop, float* fits, float* best_ind, double* best_fit,
-                        double* curves, int32_t* n_curves) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    GaIslands* s = (GaIslands*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    const int rc = gi_flush(s);   // the last generation's survivors (and its migration)
-    if (rc) return rc;
-    GGS_HIP(hipStreamSynchronize(s->st));
-    const size_t K = s->K, KP = K * s->P;
-    if (pop) GGS_HIP(hipMemcpy(pop, s->pop[s->cur].p, sizeof(float) * 9 * KP * s->N, hipMemcpyDeviceToHost));
-    if (fits) GGS_HIP(hipMemcpy(fits, s->fits[s->cur].p, sizeof(float) * KP, hipMemcpyDeviceToHost));
-    if (best_ind) GGS_HIP(hipMemcpy(best_ind, s->best_ind.p, sizeof(float) * 9 * K * s->N, hipMemcpyDeviceToHost));
-    if (best_fit) GGS_HIP(hipMemcpy(best_fit, s->best_fit.p, sizeof(double) * K, hipMemcpyDeviceToHost));
-    if (curves) {               // device [generation][K][3] -> caller [K][generation][3]
-        const size_t n = (size_t)s->n_curves;
-        std::vector<double> h(3 * K * n);
-        GGS_HIP(hipMemcpy(h.data(), s->curves.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
-        for (size_t g = 0; g < n; ++g)
-            for (size_t k = 0; k < K; ++k)
-                for (int q = 0; q < 3; ++q) curves[(k * n + g) * 3 + q] = h[(g * K + k) * 3 + q];
-    }
-    if (n_curves) *n_curves = (int32_t)s->n_curves;
-    return GGS_OK;
-}
-
-void ggs_ga_islands_destroy(void* handle) {
-    if (!handle) return;
-    GaIslands* s = (GaIslands*)handle;
-    {
-        std::lock_guard<std::mutex> lk(s->c->mu);
-        DeviceGuard dg(s->c->dev);
-        if (s->st) (void)hipStreamSynchronize(s->st);
-        gi_free(s);
-    }
-    delete s;
-}
-
-// ---- simulated annealing ------------------------------------------------------
-int ggs_sa_create(int32_t device, const ggs_ga_config* cfg, const float* target_hw3,
-                  const float* mask_hw, const float* init_ind, void** handle, float* init_fit) {
-    if (!cfg || !target_hw3 || !init_ind || !handle) return fail(GGS_EINVAL, "null argument");
-    int rc = ga_check_config(*cfg, mask_hw, true);
-    if (rc) return rc;
-    DevCtx* ctx = nullptr;
-    if ((rc = get_ctx(device, &ctx))) return rc;
-    auto s = std::make_unique<SaSession>();
-    s->c = ctx;
-    s->cfg = *cfg;
-    ga_fill_log_bounds(&s->cfg);
-    s->N = cfg->n_splats;
-    s->cap = cfg->pop_size;
-    if (const char* v = getenv("GGS_SA_DIRTY_RULE")) s->dirty_rule = atoi(v) != 0;   // A/B: 0 = genes
-    const size_t ib = sizeof(float) * 9 * (size_t)s->N, hw = (size_t)cfg->H * cfg->W;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard dg(ctx->dev);
-    auto bail = [&](int code) { sa_free(s.get()); return code; };
-    if (hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess)
-        return bail(fail(GGS_EHIP, "stream creation failed"));
-    int nTX;
-    s->nTiles = raster_tiles(cfg->H, cfg->W, &nTX);
-    const size_t slots = 4 * (size_t)s->nTiles, rb = sizeof(SplatRec) * (size_t)std::max(s->N, 1);
-    if ((rc = ensure(s->curr, std::max<size_t>(ib, 4), s->st)) || (rc = ensure(s->best, std::max<size_t>(ib, 4), s->st)) ||
-        (rc = ensure(s->nb, std::max<size_t>(ib * s->cap, 4), s->st)) ||
-        (rc = ensure(s->nb_fits, sizeof(float) * s->cap, s->st)) ||
-        (rc = ensure(s->target, sizeof(float) * 3 * hw, s->st)) ||
-        (mask_hw && (rc = ensure(s->mask, sizeof(float) * hw, s->st))) ||
-        (rc = ensure(s->cur_recs, rb, s->st)) || (rc = ensure(s->nb_recs, rb * s->cap, s->st)) ||
-        (rc = ensure(s->nb_bnds, rb / 4 * s->cap, s->st)) ||
-        (rc = ensure(s->cur_part, sizeof(float) * slots, s->st)) ||
-        (rc = ensure(s->nb_part, sizeof(float) * slots * s->cap, s->st)) ||
-        (rc = ensure(s->dirty, slots * s->cap, s->st)) || (rc = ensure(s->plan, plan_bytes(cfg->H, cfg->W), s->st)) ||
-        (rc = ensure(s->wpart, plan_wsum_bytes(cfg->H, cfg->W), s->st)) ||
-        (rc = ensure(s->order, sizeof(int) * (size_t)raster_order_len(cfg->H, cfg->W), s->st)) ||
-        (rc = ensure(s->counters, sizeof(unsigned) * 4, s->st)) || (rc = ensure(s->loop, sizeof(SaLoopDev), s->st)) ||
-        (rc = ensure(s->sizes, sizeof(float) * (size_t)std::max(s->N, 1) * s->cap, s->st)))
-        return bail(rc);
-    if (hipHostMalloc((void**)&s->h_fits, sizeof(float) * s->cap, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**)&s->h_counters, sizeof(unsigned) * 4, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**)&s->h_loop, sizeof(SaLoopDev), hipHostMallocDefault) != hipSuccess)
-        return bail(fail(GGS_ENOMEM, "pinned allocation failed"));
-    std::vector<int> order(raster_order_len(cfg->H, cfg->W));
-    raster_tile_order(cfg->H, cfg->W, order.data());
-    if (hipMemcpyAsync(s->target.p, target_hw3, sizeof(float) * 3 * hw, hipMemcpyHostToDevice, s->st) ||
-        (mask_hw && hipMemcpyAsync(s->mask.p, mask_hw, sizeof(float) * hw, hipMemcpyHostToDevice, s->st)) ||
-        hipMemcpyAsync(s->curr.p, init_ind, ib, hipMemcpyHostToDevice, s->st) ||
-        hipMemcpyAsync(s->best.p, init_ind, ib, hipMemcpyHostToDevice, s->st) ||
-        hipMemcpyAsync(s->order.p, order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice, s->st) ||
-        hipMemsetAsync(s->counters.p, 0, sizeof(unsigned) * 4, s->st))
-        return bail(fail(GGS_EHIP, "upload failed"));
-    if (launch_plan(s->st, (const float*)s->target.p, mask_hw ? (const float*)s->mask.p : nullptr,
-                    cfg->fitness_mode, cfg->boost_beta, cfg->H, cfg->W, (float4*)s->plan.p,
-                    (float*)s->wpart.p) != hipSuccess)
-        return bail(fail(GGS_EHIP, "plan launch failed"));
-    if ((rc = sa_eval(s.get(), (const float*)s->curr.p, 1, (SplatRec*)s->cur_recs.p, (int4*)s->nb_bnds.p,
-                      (float*)s->cur_part.p,
-                      (float*)s->nb_fits.p, false)))
-        return bail(rc);
-    if (hipMemcpyAsync(s->h_fits, s->nb_fits.p, sizeof(float), hipMemcpyDeviceToHost, s->st) ||
-        hipStreamSynchronize(s->st))
-        return bail(fail(GGS_EHIP, "initial evaluation failed"));
-    if (init_fit) *init_fit = s->h_fits[0];
-    // the device loop's state: current = best = the initial energy, no acceptances yet
-    *s->h_loop = SaLoopDev{};
-    s->h_loop->acc_j = -1;
-    s->h_loop->curr_fit = s->h_loop->best_fit = (double)s->h_fits[0];
-    if (hipMemcpy(s->loop.p, s->h_loop, sizeof(SaLoopDev), hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(GGS_EHIP, "upload failed"));
-    *handle = s.release();
-    return GGS_OK;
-}
-
-int ggs_sa_propose(void* handle, int32_t it, int32_t total_iters, int32_t first_try, int32_t n,
-                   const ggs_ga_draws* draws, float* fits_out) {
-    if (!handle || !fits_out) return fail(GGS_EINVAL, "null argument");
-    SaSession* s = (SaSession*)handle;
-    if (n < 1 || n > s->cap) return fail(GGS_EINVAL, "n=%d outside [1, %d]", n, s->cap);
-    if (first_try < 0) return fail(GGS_EINVAL, "first_try must be >= 0");
-    if (s->driver == 2) return fail(GGS_EINVAL, "this SA session is driven by ggs_sa_run");
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    s->driver = 1;
-    DeviceGuard dg(s->c->dev);
-    GaDrawsDev d{};
-    int rc;
-    if (draws && (rc = ga_upload_draws(s->draws, s->st, n, s->N, 1, true, draws, &d))) return rc;
-    GaParamsDev prm = ga_params(s->cfg, it, total_iters);
-    prm.mutate_only = 1;
-    prm.o_base = first_try;
-    // The neighbours and their raster records.  The variation kernel runs one
-    // workgroup per neighbour; fusing the prep into it pays while that leaves few
-    // splats per thread, but a handful of 4,096-splat neighbours (configs[4]) would
-    // prep 16 splats per thread on a few CUs (99 us): then the prep kernel runs
-    // separately, one thread per splat (same ggs_prep.h math, same bits).
-    const bool fuse_prep = s->N <= 1024 || n >= 64;
-    {
-        ProfScope ps(s->st, 0);
-        GGS_HIP(launch_ga_variation(s->st, (const float*)s->curr.p, nullptr, 1, s->N, prm, d, s->cfg.seed, it,
-                                    (float*)s->nb.p, n, fuse_prep ? (SplatRec*)s->nb_recs.p : nullptr,
-                                    (int4*)s->nb_bnds.p,
-                                    s->cfg.H, s->cfg.W, s->cfg.k_sigma));
-    }
-    if ((rc = sa_eval(s, (const float*)s->nb.p, n, (SplatRec*)s->nb_recs.p, (int4*)s->nb_bnds.p,
-                      (float*)s->nb_part.p,
-                      (float*)s->nb_fits.p, s->incremental, fuse_prep)))
-        return rc;
-    GGS_HIP(hipMemcpyAsync(s->h_fits, s->nb_fits.p, sizeof(float) * n, hipMemcpyDeviceToHost, s->st));
-    GGS_HIP(hipMemcpyAsync(s->h_counters, s->counters.p, sizeof(unsigned), hipMemcpyDeviceToHost, s->st));
-    GGS_HIP(hipMemsetAsync(s->counters.p, 0, sizeof(unsigned), s->st));
-    GGS_HIP(hipStreamSynchronize(s->st));
-    memcpy(fits_out, s->h_fits, sizeof(float) * n);
-    s->n_changed += s->h_counters[0];
-    s->n_proposed += (uint64_t)n;
-    s->last_n = n;
-    return GGS_OK;
-}
-
-int ggs_sa_commit(void* handle, int32_t j, int32_t update_best) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    SaSession* s = (SaSession*)handle;
-    if (j >= s->last_n) return fail(GGS_EINVAL, "neighbour %d not proposed (last n=%d)", j, s->last_n);
-    if (s->driver == 2) return fail(GGS_EINVAL, "this SA session is driven by ggs_sa_run");
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    const size_t ib = sizeof(float) * 9 * (size_t)s->N;
-    if (j >= 0) {   // the accepted neighbour becomes the state: genome, records, strip partials
-        const size_t rb = sizeof(SplatRec) * (size_t)s->N, pb = sizeof(float) * 4 * (size_t)s->nTiles;
-        GGS_HIP(hipMemcpyAsync(s->curr.p, (const char*)s->nb.p + ib * j, ib, hipMemcpyDeviceToDevice, s->st));
-        GGS_HIP(hipMemcpyAsync(s->cur_recs.p, (const char*)s->nb_recs.p + rb * j, rb, hipMemcpyDeviceToDevice,
-                               s->st));
-        GGS_HIP(hipMemcpyAsync(s->cur_part.p, (const char*)s->nb_part.p + pb * j, pb, hipMemcpyDeviceToDevice,
-                               s->st));
-    }
-    if (update_best) GGS_HIP(hipMemcpyAsync(s->best.p, s->curr.p, ib, hipMemcpyDeviceToDevice, s->st));
-    return GGS_OK;
-}
-
-int64_t ggs_sa_rounds_per_sync(int64_t remaining, int32_t est) {
-    const int64_t e = std::max<int64_t>(1, est);
-    const int64_t R = std::max<int64_t>(1, (std::max<int64_t>(remaining, 0) + e - 1) / e);
-    return std::min<int64_t>(R, GGS_SA_MAX_ROUNDS_PER_SYNC);
-}
-
-// Diagnostic override of the bound (tools/probe/sa_pmc_r03b.sh reproduces the
-// round-2 crash with it lifted); not part of the C ABI.
-static int64_t sa_rounds_per_sync(int64_t remaining, int32_t est) {
-    static const int64_t cap = [] {
-        const char* v = getenv("GGS_SA_MAX_ROUNDS_PER_SYNC");
-        return v ? std::max<int64_t>(1, atoll(v)) : (int64_t)0;
-    }();
-    if (!cap) return ggs_sa_rounds_per_sync(remaining, est);
-    const int64_t e = std::max<int64_t>(1, est);
-    return std::min<int64_t>(cap, std::max<int64_t>(1, (std::max<int64_t>(remaining, 0) + e - 1) / e));
-}
-
-int ggs_sa_run(void* handle, int32_t first_it, int32_t n_its, int32_t total_iters, int32_t tries,
-               const double* temps, int32_t width, double* curves_out) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    SaSession* s = (SaSession*)handle;
-    if (first_it < 0 || n_its < 0 || tries < 1) return fail(GGS_EINVAL, "need first_it >= 0, n_its >= 0, tries >= 1");
-    if (n_its > 0 && (!temps || !curves_out)) return fail(GGS_EINVAL, "null temps / curves");
-    if (width < 0 || width > s->cap) return fail(GGS_EINVAL, "width=%d outside [0, %d]", width, s->cap);
-    if ((int64_t)(first_it + (int64_t)n_its) * tries > INT32_MAX)
-        return fail(GGS_EINVAL, "iterations x tries must stay below 2^31");
-    if (s->driver == 1) return fail(GGS_EINVAL, "this SA session is driven by ggs_sa_propose/commit");
-    if (n_its == 0) return GGS_OK;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    s->driver = 2;
-    if (!s->incremental) s->cur_cache_valid = false;
-    const ggs_ga_config& c = s->cfg;
-    std::vector<SaItDev> tab((size_t)n_its);
-    for (int i = 0; i < n_its; ++i) {
-        const GaParamsDev q = ga_params(c, first_it + i, total_iters);
-        tab[i] = SaItDev{{q.sig_xy, q.sig_alog, q.sig_blog, q.sig_theta, q.sig_rgb, q.sig_alpha}, {0.f, 0.f},
-                         temps[i]};
-    }
-    int rc;
-    if ((rc = ensure(s->sit, sizeof(SaItDev) * (size_t)n_its, s->st)) ||
-        (rc = ensure(s->curves, sizeof(double) * 2 * (size_t)n_its, s->st)))
-        return rc;
-    SaLoopDev* loop = (SaLoopDev*)s->loop.p;
-    const SaItDev* sit = (const SaItDev*)s->sit.p;
-    double* curves = (double*)s->curves.p;
-    GGS_HIP(hipMemcpyAsync(s->sit.p, tab.data(), sizeof(SaItDev) * (size_t)n_its, hipMemcpyHostToDevice, s->st));
-    const int64_t pos0 = (int64_t)first_it * tries, end = pos0 + (int64_t)n_its * tries;
-    // adaptive width (sa_width_rule): a round's fixed cost in neighbour evaluations,
-    // half the number of candidates whose strip waves fit in the GPU's raster wave
-    // slots (CUs x 4 SIMDs x 3 waves): small canvases add neighbours almost for free
-    // until the chip fills.  2048^2 (2,048 strips): 0.75 — measured at configs[4],
-    // start of a run, a round of 1 neighbour costs 191 us and of 2 297 us (r = 0.81);
-    // 512^2 (128 strips): 12
-    static const double wave_slots = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess)
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        return 12.0 * (double)cus;
-    }();
-    const double width_r = std::max(0.25, 0.5 * wave_slots / (double)(4 * s->nTiles));
-    // Width of a batch of rounds: the rule's width at the acceptance rate of the
-    // last sync, used by every round of the batch and the size of their mutation
-    // and raster grids — not the session capacity with the width chosen per round
-    // on the device: unused neighbour slots are not free (a lone 2048^2 neighbour in
-    // a 16-slot grid ran 216 us per round instead of 191: the early-exit strip waves
-    // of the other slots stream through the free wave slots beside it).  The
-    // pending round (computed by the previous batch) keeps its width; the
-    // trajectory does not depend on the width.
-    auto batch_width = [&]() {
-        const int w = width > 0 ? width : sa_width_rule(s->h_loop->acc_rate, s->cap, width_r);
-        return std::min(s->cap, std::max(w, 1));
-    };
-    int bw = batch_width(), gcap = bw;
-    GGS_HIP(launch_sa_begin(s->st, loop, pos0, end, tries, first_it, s->cap, width, width_r, bw));
-    if ((rc = ensure(s->flags, sizeof(int) * (size_t)(end - pos0), s->st))) return rc;
-    GGS_HIP(launch_sa_flags(s->st, pos0, (int)(end - pos0), tries, c.seed, c.mutpb, s->N, (int*)s->flags.p));
-    GaParamsDev prm = ga_params(c, first_it, total_iters);   // sigmas replaced per neighbour from sit
-    prm.mutate_only = 1;
-    prm.o_base = 0;
-    const int nslots = 4 * s->nTiles;
-    const float bg[3] = {1.f, 1.f, 1.f};
-    const int* live = &loop->live;
-    SaRoundDev rd{};
-    rd.partials = (const float*)s->nb_part.p;
-    rd.wpartials = (const float*)s->wpart.p;
-    rd.nslots = nslots;
-    rd.mode = c.fitness_mode;
-    rd.N = s->N;
-    rd.hw = (double)c.H * (double)c.W;
-    rd.fits_out = (float*)s->nb_fits.p;
-    rd.seed = c.seed;
-    rd.mutpb = c.mutpb;
-    rd.curves = curves;
-    rd.curr = (float*)s->curr.p;
-    rd.best = (float*)s->best.p;
-    rd.nb = (const float*)s->nb.p;
-    rd.cur_recs = s->incremental ? (SplatRec*)s->cur_recs.p : nullptr;
-    rd.nb_recs = (const SplatRec*)s->nb_recs.p;
-    rd.cur_part = (float*)s->cur_part.p;
-    // one round: mutate (+ records) and swap, [dirty strips], raster, then one
-    // workgroup for fitness, acceptance, install and the next round's flags
-    auto round = [&]() -> int {
-        {
-            ProfScope ps(s->st, 0);
-            GGS_HIP(launch_sa_mutate(s->st, loop, sit, prm, c.seed, s->N, gcap, (int*)s->flags.p,
-                                     (const float*)s->curr.p, (float*)s->nb.p, (float*)s->sizes.p,
-                                     (SplatRec*)s->nb_recs.p, (int4*)s->nb_bnds.p, c.H, c.W, c.k_sigma));
-        }
-        if (s->incremental)
-            GGS_HIP(launch_dirty(s->st, (const float*)s->curr.p, (const float*)s->nb.p,
-                                 (const SplatRec*)s->cur_recs.p, (const SplatRec*)s->nb_recs.p, gcap, s->N, c.H,
-                                 c.W, (unsigned char*)s->dirty.p, (unsigned*)s->counters.p, live, s->dirty_rule));
-        {
-            ProfScope ps(s->st, 1);
-            GGS_HIP(launch_raster(s->st, 1, (const SplatRec*)s->nb_recs.p, (const int4*)s->nb_bnds.p, gcap, s->N,
-                                  c.H, c.W, bg, nullptr,
-                                  (const float4*)s->plan.p, (float*)s->nb_part.p, (const int*)s->order.p,
-                                  s->incremental ? (const unsigned char*)s->dirty.p : nullptr,
-                                  (const float*)s->cur_part.p, live, nullptr, s->c->simds));
-        }
-        rd.gcap = bw;
-        GGS_HIP(launch_sa_accept(s->st, loop, sit, rd));
-        return GGS_OK;
-    };
-    // Rounds are enqueued in batches with one host sync between batches: a round
-    // consumes at most its width in tries, so ceil(remaining / width) rounds never
-    // overshoot the chunk (rounds past its end would be empty launches anyway).
-    // A batch holds at most GGS_SA_MAX_ROUNDS_PER_SYNC rounds (ggs_sa_rounds_per_sync):
-    // unbounded, a 256-iteration chunk at high acceptance queued ~1,000 rounds =
-    // 4,000 dispatches behind one sync, and rocprofv3's PMC dispatch interception
-    // crashed the host thread inside the launch call (docs/EXPERIMENTS.md §9).
-    const uint64_t evaluated0 = s->h_loop->evaluated;
-    int64_t remaining = end - pos0;
-    int est = gcap;
-    for (;;) {
-        int64_t R = sa_rounds_per_sync(remaining, est);
-        // the batch width comes from the acceptance rate at this sync: while the
-        // rate has little history (a session's first tries) sync every 2 rounds
-        if (s->h_loop->evaluated < 64) R = std::min<int64_t>(R, 2);
-        for (int64_t r = 0; r < R; ++r) {
-            if ((rc = round())) return rc;
-            gcap = bw;                  // after the pending round: every round has width bw
-        }
-        GGS_HIP(hipMemcpyAsync(s->h_loop, loop, sizeof(SaLoopDev), hipMemcpyDeviceToHost, s->st));
-        GGS_HIP(hipStreamSynchronize(s->st));
-        if (s->h_loop->pos >= end) break;
-        remaining = end - s->h_loop->pos;
-        bw = batch_width();
-        gcap = std::max(bw, (int)s->h_loop->live);     // the grids also hold the pending round
-        est = std::max(1, (int)s->h_loop->live);
-    }
-    GGS_HIP(hipMemcpyAsync(curves_out, curves, sizeof(double) * 2 * (size_t)n_its, hipMemcpyDeviceToHost, s->st));
-    if (s->incremental) {
-        GGS_HIP(hipMemcpyAsync(s->h_counters, s->counters.p, sizeof(unsigned), hipMemcpyDeviceToHost, s->st));
-        GGS_HIP(hipMemsetAsync(s->counters.p, 0, sizeof(unsigned), s->st));
-    }
-    GGS_HIP(hipStreamSynchronize(s->st));
-    if (s->incremental) s->n_changed += s->h_counters[0];
-    s->n_proposed += s->h_loop->evaluated - evaluated0;
-    return GGS_OK;
-}
-
-int ggs_sa_loop_state(void* handle, double* best_fit, double* curr_fit, uint64_t* rounds, uint64_t* evaluated,
-                      uint64_t* accepted) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    SaSession* s = (SaSession*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    const SaLoopDev& l = *s->h_loop;     // as of the end of the last ggs_sa_run (or creation)
-    if (best_fit) *best_fit = l.best_fit;
-    if (curr_fit) *curr_fit = l.curr_fit;
-    if (rounds) *rounds = l.rounds;
-    if (evaluated) *evaluated = l.evaluated;
-    if (accepted) *accepted = l.accepted;
-    return GGS_OK;
-}
-
-int ggs_sa_accept_uniform(uint64_t seed, int32_t it, int32_t k, double* u) {
-    if (!u || it < 0 || k < 0) return fail(GGS_EINVAL, "bad arguments");
-    *u = sa_accept_uniform(seed, (uint32_t)it, (uint32_t)k);
-    return GGS_OK;
-}
-
-int ggs_ga_philox_draws(int32_t device, uint64_t seed, int32_t gen, int32_t first, int32_t n_off, int32_t P,
-                        int32_t N, int32_t tour_k, float cxpb, const ggs_ga_draws_out* out) {
-    if (n_off < 1 || P < 1 || N < 1 || tour_k < 1)
-        return fail(GGS_EINVAL, "n_off=%d, P=%d, N=%d, tour_k=%d must be >= 1", n_off, P, N, tour_k);
-    if (gen < 0 || first < 0) return fail(GGS_EINVAL, "gen=%d, first=%d must be >= 0", gen, first);
-    const int64_t on = (int64_t)n_off * N, np2 = (n_off + 1) / 2;
-    if (on > ((int64_t)1 << 27) || (int64_t)P * tour_k > ((int64_t)1 << 27))
-        return fail(GGS_EINVAL, "n_off*N=%lld, P*tour_k=%lld exceed the limit of 2^27 draws per array",
-                    (long long)on, (long long)P * tour_k);
-    if (!out) return fail(GGS_EINVAL, "null output");
-    GaDrawsOut d{};
-    struct Seg { void* host; int64_t bytes; void** dev; };
-    Seg segs[] = {
-        {out->tour_idx, 4 * (int64_t)P * tour_k, (void**)&d.tour_idx}, {out->perm, 4 * (int64_t)P, (void**)&d.perm},
-        {out->cx, 4 * np2, (void**)&d.cx}, {out->cx_u, 4 * np2 * N, (void**)&d.cx_u},
-        {out->u_xy, 8 * on, (void**)&d.u_xy}, {out->u_ab, 8 * on, (void**)&d.u_ab},
-        {out->u_t, 4 * on, (void**)&d.u_t}, {out->u_rgb, 4 * on, (void**)&d.u_rgb},
-        {out->u_a, 4 * on, (void**)&d.u_a}, {out->k_color, 4 * (int64_t)n_off, (void**)&d.k_color},
-        {out->k_xy, 4 * (int64_t)n_off, (void**)&d.k_xy}, {out->k_ab, 4 * (int64_t)n_off, (void**)&d.k_ab},
-        {out->k_t, 4 * (int64_t)n_off, (void**)&d.k_t}, {out->n_xy, 8 * on, (void**)&d.n_xy},
-        {out->n_ab, 8 * on, (void**)&d.n_ab}, {out->n_t, 4 * on, (void**)&d.n_t},
-        {out->n_rgba, 16 * on, (void**)&d.n_rgba}, {out->swap_i, 4 * (int64_t)n_off, (void**)&d.swap_i},
-        {out->swap_pick, 4 * (int64_t)n_off, (void**)&d.swap_pick},
-        {out->swap_u, 8 * (int64_t)n_off, (void**)&d.swap_u},
-    };
-    int64_t total = 0;
-    for (const Seg& g : segs) {
-        if (!g.host) return fail(GGS_EINVAL, "null output: every draws array is required");
-        total += (g.bytes + 255) & ~(int64_t)255;
-    }
-    int rc;
-    DevCtx* c = nullptr;
-    if ((rc = get_ctx(device, &c))) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard dg(c->dev);
-    struct Scratch {
-        void* p = nullptr;
-        ~Scratch() { if (p) (void)hipFree(p); }
-    } buf;
-    GGS_HIP(hipMalloc(&buf.p, (size_t)total));
-    char* base = (char*)buf.p;
-    for (const Seg& g : segs) {
-        *g.dev = base;
-        base += (g.bytes + 255) & ~(int64_t)255;
-    }
-    GGS_HIP(launch_ga_philox_draws(c->stream, seed, gen, first, n_off, P, N, tour_k, cxpb, d));
-    GGS_HIP(hipStreamSynchronize(c->stream));
-    for (const Seg& g : segs) GGS_HIP(hipMemcpy(g.host, *g.dev, (size_t)g.bytes, hipMemcpyDeviceToHost));
-    return GGS_OK;
-}
-
-int ggs_sa_set_incremental(void* handle, int32_t on) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    SaSession* s = (SaSession*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    if (on && !s->incremental && !s->cur_cache_valid) {
-        // The device loop installs an accepted neighbour's records and strip
-        // partials only while incremental evaluation is on (sa_accept_kernel), so
-        // after an incremental-off ggs_sa_run they describe an older state:
-        // re-evaluate the current state before the dirty-strip test relies on them.
-        // (Right after create, or after propose/commit, they are current: no work.)
-        DeviceGuard dg(s->c->dev);
-        int rc = sa_eval(s, (const float*)s->curr.p, 1, (SplatRec*)s->cur_recs.p, (int4*)s->nb_bnds.p,
-                         (float*)s->cur_part.p, (float*)s->nb_fits.p, false);
-        if (rc) return rc;
-        GGS_HIP(hipStreamSynchronize(s->st));
-        s->cur_cache_valid = true;
-    }
-    s->incremental = on != 0;
-    return GGS_OK;
-}
-
-int ggs_sa_stats(void* handle, uint64_t* proposed, uint64_t* changed_splats) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    SaSession* s = (SaSession*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    if (proposed) *proposed = s->n_proposed;
-    if (changed_splats) *changed_splats = s->n_changed;
-    return GGS_OK;
-}
-
-int ggs_sa_read(void* handle, float* current, float* best, float* neighbours) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    SaSession* s = (SaSession*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    const size_t ib = sizeof(float) * 9 * (size_t)s->N;
-    GGS_HIP(hipStreamSynchronize(s->st));
-    if (current) GGS_HIP(hipMemcpy(current, s->curr.p, ib, hipMemcpyDeviceToHost));
-    if (best) GGS_HIP(hipMemcpy(best, s->best.p, ib, hipMemcpyDeviceToHost));
-    if (neighbours && s->last_n > 0)
-        GGS_HIP(hipMemcpy(neighbours, s->nb.p, ib * s->last_n, hipMemcpyDeviceToHost));
-    return GGS_OK;
-}
-
-void ggs_sa_destroy(void* handle) {
-    if (!handle) return;
-    SaSession* s = (SaSession*)handle;
-    {
-        std::lock_guard<std::mutex> lk(s->c->mu);
-        DeviceGuard dg(s->c->dev);
-        if (s->st) (void)hipStreamSynchronize(s->st);
-        sa_free(s);
-    }
-    delete s;
-}
-
-}  // extern "C"
-
-// ---- SA chain groups -------------------------------------------------------------
-namespace ggs {
-namespace {
-
-struct SaChains {
-    DevCtx* c = nullptr;
-    hipStream_t st = nullptr;
-    ggs_ga_config cfg{};
-    int K = 0, N = 0, cap = 0, nTiles = 0, exchange_every = 0;
-    bool multi = false;             // a target (plan) per chain
-    uint64_t exchange_seed = 0;
-    int64_t gstride = 0;            // floats between the chains' genomes in curr / best
-    DevBuf curr, best, nb, nb_fits, target, mask, nb_recs, nb_bnds, nb_part, plan, wpart, order, fctr;
-    DevBuf loop, sit, curves, flags, sizes, seeds, list, swaps;
-    SaLoopDev* h_loop = nullptr;    // pinned [K]
-    float* h_fits = nullptr;        // pinned [K]
-    unsigned long long* h_swaps = nullptr;   // pinned [2]: exchange pairs tried / swapped
-};
-
-void sc_free(SaChains* s) {
-    for (DevBuf* b : {&s->curr, &s->best, &s->nb, &s->nb_fits, &s->target, &s->mask, &s->nb_recs, &s->nb_bnds,
-                      &s->nb_part, &s->plan, &s->wpart, &s->order, &s->fctr, &s->loop, &s->sit, &s->curves, &s->flags,
-                      &s->sizes, &s->seeds, &s->list, &s->swaps})
-        if (b->p) (void)hipFree(b->p);
-    if (s->h_loop) (void)hipHostFree(s->h_loop);
-    if (s->h_fits) (void)hipHostFree(s->h_fits);
-    if (s->h_swaps) (void)hipHostFree(s->h_swaps);
-    if (s->st) (void)hipStreamDestroy(s->st);
-}
-
-SaChainsDev sc_dev(const SaChains* s, int n_its, int n_tries) {
-    SaChainsDev g{};
-    g.K = s->K;
-    g.n_its = n_its;
-    g.n_tries = n_tries;
-    g.cap = s->cap;
-    g.gstride = s->gstride;
-    g.wstride = s->multi ? (int64_t)(plan_wsum_bytes(s->cfg.H, s->cfg.W) / sizeof(float)) : 0;
-    g.seeds = (const uint64_t*)s->seeds.p;
-    int* l = (int*)s->list.p;       // total (+ 3 of padding), base [K], chain [K * cap], slot [K * cap]
-    g.total = l;
-    g.base = l + 4;
-    g.chain = g.base + s->K;
-    g.slot = g.chain + (size_t)s->K * s->cap;
-    return g;
-}
-
-int sc_check(const ggs_ga_config* cfg, const ggs_sa_chains* ch, const float* target, const float* mask,
-             const float* init_inds, void** handle, bool multi) {
-    if (!cfg || !ch || !target || !init_inds || !handle) return fail(GGS_EINVAL, "null argument");
-    int rc = ga_check_config(*cfg, mask, true);
-    if (rc) return rc;
-    if (ch->n_chains < 1 || ch->n_chains > GGS_SA_MAX_CHAINS)
-        return fail(GGS_EINVAL, "n_chains must be in [1, %d], got %d", GGS_SA_MAX_CHAINS, ch->n_chains);
-    if (!ch->seeds) return fail(GGS_EINVAL, "seeds is required ([n_chains])");
-    if (ch->exchange_every < 0) return fail(GGS_EINVAL, "exchange_every must be >= 0, got %d", ch->exchange_every);
-    if (multi && ch->exchange_every > 0)
-        return fail(GGS_EINVAL, "replica exchange needs one shared target: an energy measured on another image "
-                                "means nothing (exchange_every=%d)", ch->exchange_every);
-    return check_dims((int64_t)ch->n_chains * cfg->pop_size, cfg->n_splats, 9, cfg->H, cfg->W);
-}
-
-int sc_create(int32_t device, const ggs_ga_config* cfg, const ggs_sa_chains* ch, const float* target,
-              const float* mask, const float* init_inds, void** handle, float* init_fits, bool multi) {
-    int rc = sc_check(cfg, ch, target, mask, init_inds, handle, multi);   // before any device call
-    if (rc) return rc;
-    const ggs_ga_config& c = *cfg;
-    DevCtx* ctx = nullptr;
-    if ((rc = get_ctx(device, &ctx))) return rc;
-    auto s = std::make_unique<SaChains>();
-    s->c = ctx;
-    s->cfg = c;
-    ga_fill_log_bounds(&s->cfg);
-    const int K = s->K = ch->n_chains, N = s->N = c.n_splats;
-    s->cap = c.pop_size;
-    s->multi = multi;
-    s->exchange_every = ch->exchange_every;
-    s->exchange_seed = ch->exchange_seed;
-    const size_t n9 = 9 * (size_t)N;
-    s->gstride = (int64_t)((n9 + 3) & ~(size_t)3);
-    const size_t nplans = multi ? (size_t)K : 1, hw = nplans * (size_t)c.H * c.W;
-    const size_t B = (size_t)K * s->cap, BN = B * (size_t)std::max(N, 1);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard dg(ctx->dev);
-    auto bail = [&](int code) {
-        const std::string keep = t_err;
-        if (s->st) (void)hipStreamSynchronize(s->st);
-        sc_free(s.get());
-        t_err = keep;
-        return code;
-    };
-    if (hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess)
-        return bail(fail(GGS_EHIP, "stream creation failed"));
-    int nTX;
-    s->nTiles = raster_tiles(c.H, c.W, &nTX);
-    const size_t slots = 4 * (size_t)s->nTiles, gb = sizeof(float) * std::max<size_t>((size_t)s->gstride * K, 4);
-    if ((rc = ensure(s->curr, gb, s->st)) || (rc = ensure(s->best, gb, s->st)) ||
-        (rc = ensure(s->nb, sizeof(float) * std::max<size_t>(n9 * B, 4), s->st)) ||
-        (rc = ensure(s->nb_fits, sizeof(float) * B, s->st)) ||
-        (rc = ensure(s->target, sizeof(float) * 3 * hw, s->st)) ||
-        (mask && (rc = ensure(s->mask, sizeof(float) * hw, s->st))) ||
-        (rc = ensure(s->nb_recs, sizeof(SplatRec) * BN, s->st)) || (rc = ensure(s->nb_bnds, sizeof(int4) * BN, s->st)) ||
-        (rc = ensure(s->nb_part, sizeof(float) * slots * B, s->st)) ||
-        (rc = ensure(s->plan, nplans * plan_bytes(c.H, c.W), s->st)) ||
-        (rc = ensure(s->wpart, nplans * plan_wsum_bytes(c.H, c.W), s->st)) ||
-        (rc = ensure(s->order, sizeof(int) * (size_t)raster_order_len(c.H, c.W), s->st)) ||
-        (rc = ensure(s->loop, sizeof(SaLoopDev) * K, s->st)) || (rc = ensure(s->sizes, sizeof(float) * BN, s->st)) ||
-        (rc = ensure(s->seeds, sizeof(uint64_t) * K, s->st)) ||
-        (rc = ensure_zeroed(s->list, sizeof(int) * (4 + (size_t)K + 2 * B), s->st)) ||
-        (rc = ensure_zeroed(s->swaps, sizeof(unsigned long long) * 2, s->st)))
-        return bail(rc);
-    if (hipHostMalloc((void**)&s->h_fits, sizeof(float) * K, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**)&s->h_swaps, sizeof(unsigned long long) * 2, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**)&s->h_loop, sizeof(SaLoopDev) * K, hipHostMallocDefault) != hipSuccess)
-        return bail(fail(GGS_ENOMEM, "pinned allocation failed"));
-    s->h_swaps[0] = s->h_swaps[1] = 0;
-    std::vector<int> order(raster_order_len(c.H, c.W));
-    raster_tile_order(c.H, c.W, order.data());
-    // the K initial individuals, contiguous in the neighbour buffer for their one evaluation
-    if (hipMemcpyAsync(s->target.p, target, sizeof(float) * 3 * hw, hipMemcpyHostToDevice, s->st) ||
-        (mask && hipMemcpyAsync(s->mask.p, mask, sizeof(float) * hw, hipMemcpyHostToDevice, s->st)) ||
-        hipMemcpyAsync(s->nb.p, init_inds, sizeof(float) * n9 * K, hipMemcpyHostToDevice, s->st) ||
-        hipMemcpyAsync(s->seeds.p, ch->seeds, sizeof(uint64_t) * K, hipMemcpyHostToDevice, s->st) ||
-        hipMemcpyAsync(s->order.p, order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice, s->st))
-        return bail(fail(GGS_EHIP, "upload failed"));
-    for (int k = 0; k < K && n9; ++k)
-        if (hipMemcpyAsync((float*)s->curr.p + k * s->gstride, init_inds + n9 * k, sizeof(float) * n9,
-                           hipMemcpyHostToDevice, s->st) ||
-            hipMemcpyAsync((float*)s->best.p + k * s->gstride, init_inds + n9 * k, sizeof(float) * n9,
-                           hipMemcpyHostToDevice, s->st))
-            return bail(fail(GGS_EHIP, "upload failed"));
-    if (launch_plan_set(s->st, (const float*)s->target.p, mask ? (const float*)s->mask.p : nullptr, c.fitness_mode,
-                        c.boost_beta, c.H, c.W, (int)nplans, (float4*)s->plan.p, (float*)s->wpart.p) != hipSuccess)
-        return bail(fail(GGS_EHIP, "plan launch failed"));
-    // one prep and one raster launch for the K initial energies (chain k against
-    // plan k of a plan set: group 1); unfused, as ggs_sa_create evaluates its one
-    if (launch_prep(s->st, true, (const float*)s->nb.p, (int64_t)K * N, 9, c.H, c.W, c.k_sigma, (SplatRec*)s->nb_recs.p,
-                    (int4*)s->nb_bnds.p, nullptr, nullptr, nullptr) != hipSuccess)
-        return bail(fail(GGS_EHIP, "prep launch failed"));
-    if ((rc = raster_fitness(s->st, ctx->simds, (const SplatRec*)s->nb_recs.p, (const int4*)s->nb_bnds.p, K, N, c.H, c.W,
-                             (const float4*)s->plan.p, (float*)s->nb_part.p, (const float*)s->wpart.p, c.fitness_mode,
-                             (const int*)s->order.p, s->fctr, (float*)s->nb_fits.p, false, nullptr, nullptr,
-                             multi ? 1 : 0)))
-        return bail(rc);
-    if (hipMemcpyAsync(s->h_fits, s->nb_fits.p, sizeof(float) * K, hipMemcpyDeviceToHost, s->st) ||
-        hipStreamSynchronize(s->st))
-        return bail(fail(GGS_EHIP, "initial evaluation failed"));
-    for (int k = 0; k < K; ++k) {
-        if (init_fits) init_fits[k] = s->h_fits[k];
-        s->h_loop[k] = SaLoopDev{};
-        s->h_loop[k].acc_j = -1;
-        s->h_loop[k].curr_fit = s->h_loop[k].best_fit = (double)s->h_fits[k];
-    }
-    if (hipMemcpy(s->loop.p, s->h_loop, sizeof(SaLoopDev) * K, hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(GGS_EHIP, "upload failed"));
-    *handle = s.release();
-    return GGS_OK;
-}
-
-// One chunk of iterations [first_it, first_it + n) for every chain, no exchange
-// inside it.  temps[k * tstride + i], curves_out[(k * tstride + i) * 2 + {0, 1}].
-int sc_run_chunk(SaChains* s, int first_it, int n, int total_iters, int tries, const double* temps, int tstride,
-                 int width, double* curves_out) {
-    const ggs_ga_config& c = s->cfg;
-    const int K = s->K;
-    std::vector<SaItDev> tab((size_t)K * n);
-    for (int i = 0; i < n; ++i) {
-        const GaParamsDev q = ga_params(c, first_it + i, total_iters);
-        for (int k = 0; k < K; ++k)
-            tab[(size_t)k * n + i] = SaItDev{{q.sig_xy, q.sig_alog, q.sig_blog, q.sig_theta, q.sig_rgb, q.sig_alpha},
-                                             {0.f, 0.f}, temps[(size_t)k * tstride + i]};
-    }
-    const int64_t pos0 = (int64_t)first_it * tries, end = pos0 + (int64_t)n * tries;
-    const int n_tries = (int)(end - pos0);
-    int rc;
-    if ((rc = ensure(s->sit, sizeof(SaItDev) * tab.size(), s->st)) ||
-        (rc = ensure(s->curves, sizeof(double) * 2 * tab.size(), s->st)) ||
-        (rc = ensure(s->flags, sizeof(int) * (size_t)n_tries * K, s->st)))
-        return rc;
-    const SaChainsDev g = sc_dev(s, n, n_tries);
-    SaLoopDev* loop = (SaLoopDev*)s->loop.p;
-    const SaItDev* sit = (const SaItDev*)s->sit.p;
-    GGS_HIP(hipMemcpyAsync(s->sit.p, tab.data(), sizeof(SaItDev) * tab.size(), hipMemcpyHostToDevice, s->st));
-    // Adaptive width for the group: the lone session's rule with the
-    // round's fixed cost (ggs_sa_run's width_r, in neighbour evaluations) divided
-    // by the number of unfinished chains, which share that round, at the mean
-    // acceptance rate of those chains.  One width per batch for all chains.
-    static const double wave_slots = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess)
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        return 12.0 * (double)cus;
-    }();
-    const double width_r = std::max(0.25, 0.5 * wave_slots / (double)(4 * s->nTiles));
-    bool fresh = true;              // before the chunk's first sync: every chain is unfinished
-    auto unfinished = [&](int k) { return fresh || s->h_loop[k].pos < end; };
-    auto batch_width = [&]() {
-        if (width > 0) return std::min(s->cap, width);
-        double p = 0.0;
-        int u = 0;
-        for (int k = 0; k < K; ++k)
-            if (unfinished(k)) { p += s->h_loop[k].acc_rate; ++u; }
-        u = std::max(u, 1);
-        return std::min(s->cap, std::max(1, sa_width_rule(p / u, s->cap, width_r / u)));
-    };
-    int bw = batch_width(), gcap = bw;
-    GGS_HIP(launch_sa_chains_begin(s->st, g, loop, pos0, end, tries, first_it, width, width_r, bw));
-    GGS_HIP(launch_sa_chains_flags(s->st, g, pos0, tries, c.mutpb, s->N, (int*)s->flags.p));
-    GaParamsDev prm = ga_params(c, first_it, total_iters);   // sigmas replaced per neighbour from sit
-    prm.mutate_only = 1;
-    prm.o_base = 0;
-    const float bg[3] = {1.f, 1.f, 1.f};
-    SaRoundDev rd{};
-    rd.partials = (const float*)s->nb_part.p;
-    rd.wpartials = (const float*)s->wpart.p;
-    rd.nslots = 4 * s->nTiles;
-    rd.mode = c.fitness_mode;
-    rd.N = s->N;
-    rd.hw = (double)c.H * (double)c.W;
-    rd.fits_out = (float*)s->nb_fits.p;
-    rd.mutpb = c.mutpb;
-    rd.curves = (double*)s->curves.p;
-    rd.curr = (float*)s->curr.p;
-    rd.best = (float*)s->best.p;
-    rd.nb = (const float*)s->nb.p;
-    // one round: mutate + swap over the listed neighbours, one raster launch over
-    // exactly that many candidates, the chains' accept workgroups, the next list
-    auto round = [&]() -> int {
-        const int B = K * gcap;
-        {
-            ProfScope ps(s->st, 0);
-            GGS_HIP(launch_sa_chains_mutate(s->st, g, loop, sit, prm, s->N, B, (const int*)s->flags.p,
-                                            (const float*)s->curr.p, (float*)s->nb.p, (float*)s->sizes.p,
-                                            (SplatRec*)s->nb_recs.p, (int4*)s->nb_bnds.p, c.H, c.W, c.k_sigma));
-        }
-        {
-            ProfScope ps(s->st, 1);
-            if (s->multi)
-                GGS_HIP(launch_chain_strips(s->st, (const SplatRec*)s->nb_recs.p, (const int4*)s->nb_bnds.p, B, s->N,
-                                            c.H, c.W, (const float4*)s->plan.p, (float*)s->nb_part.p,
-                                            (const int*)s->order.p, g.total, g.chain, s->c->simds));
-            else
-                GGS_HIP(launch_raster(s->st, 1, (const SplatRec*)s->nb_recs.p, (const int4*)s->nb_bnds.p, B, s->N, c.H,
-                                      c.W, bg, nullptr, (const float4*)s->plan.p, (float*)s->nb_part.p,
-                                      (const int*)s->order.p, nullptr, nullptr, g.total, nullptr, s->c->simds));
-        }
-        rd.gcap = bw;
-        GGS_HIP(launch_sa_chains_accept(s->st, g, loop, sit, rd));
-        return GGS_OK;
-    };
-    // Batches of rounds with one host sync between them, as ggs_sa_run: the batch
-    // ends when every chain's pos >= end, a round consumes at most its width of a
-    // chain's tries, so ceil(longest remaining / width) rounds never overshoot.
-    int64_t remaining = end - pos0;
-    int est = gcap;
-    for (;;) {
-        int64_t R = sa_rounds_per_sync(remaining, est);
-        uint64_t ev = UINT64_MAX;
-        for (int k = 0; k < K; ++k)
-            if (unfinished(k)) ev = std::min<uint64_t>(ev, s->h_loop[k].evaluated);
-        if (ev < 64) R = std::min<int64_t>(R, 2);      // little acceptance history yet
-        for (int64_t r = 0; r < R; ++r) {
-            if ((rc = round())) return rc;
-            gcap = bw;                  // after the pending round: every round has width bw
-        }
-        GGS_HIP(hipMemcpyAsync(s->h_loop, loop, sizeof(SaLoopDev) * K, hipMemcpyDeviceToHost, s->st));
-        GGS_HIP(hipStreamSynchronize(s->st));
-        fresh = false;
-        remaining = 0;
-        int live = 1;
-        for (int k = 0; k < K; ++k) {
-            remaining = std::max<int64_t>(remaining, end - s->h_loop[k].pos);
-            live = std::max(live, (int)s->h_loop[k].live);
-        }
-        if (remaining <= 0) break;
-        bw = batch_width();
-        gcap = std::max(bw, live);      // the grids also hold the pending round
-        est = gcap;
-    }
-    std::vector<double> h(2 * tab.size());
-    GGS_HIP(hipMemcpyAsync(h.data(), s->curves.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s->st));
-    GGS_HIP(hipStreamSynchronize(s->st));
-    for (int k = 0; k < K; ++k)
-        memcpy(curves_out + 2 * (size_t)k * tstride, h.data() + 2 * (size_t)k * n, sizeof(double) * 2 * (size_t)n);
-    return GGS_OK;
-}
-
-}  // namespace
-}  // namespace ggs
-
-extern "C" {
-
-int ggs_sa_chains_create(int32_t device, const ggs_ga_config* cfg, const ggs_sa_chains* chains,
-                         const float* target_hw3, const float* mask_hw, const float* init_inds, void** handle,
-                         float* init_fits) {
-    return ggs::sc_create(device, cfg, chains, target_hw3, mask_hw, init_inds, handle, init_fits, false);
-}
-
-int ggs_sa_chains_create_targets(int32_t device, const ggs_ga_config* cfg, const ggs_sa_chains* chains,
-                                 const float* targets_khw3, const float* masks_khw, const float* init_inds,
-                                 void** handle, float* init_fits) {
-    return ggs::sc_create(device, cfg, chains, targets_khw3, masks_khw, init_inds, handle, init_fits, true);
-}
-
-int ggs_sa_chains_run(void* handle, int32_t first_it, int32_t n_its, int32_t total_iters, int32_t tries,
-                      const double* temps, int32_t width, double* curves_out) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    SaChains* s = (SaChains*)handle;
-    if (first_it < 0 || n_its < 0 || tries < 1) return fail(GGS_EINVAL, "need first_it >= 0, n_its >= 0, tries >= 1");
-    if (n_its > 0 && (!temps || !curves_out)) return fail(GGS_EINVAL, "null temps / curves");
-    if (width < 0 || width > s->cap) return fail(GGS_EINVAL, "width=%d outside [0, %d]", width, s->cap);
-    if ((int64_t)(first_it + (int64_t)n_its) * tries > INT32_MAX)
-        return fail(GGS_EINVAL, "iterations x tries must stay below 2^31");
-    if (n_its == 0) return GGS_OK;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    // the range in chunks that end where an exchange is due (all of it without exchange)
-    const int M = s->K >= 2 ? s->exchange_every : 0;
-    for (int done = 0; done < n_its;) {
-        const int it0 = first_it + done;
-        int n = n_its - done;
-        if (M > 0) n = std::min(n, M - it0 % M);
-        int rc = sc_run_chunk(s, it0, n, total_iters, tries, temps + done, n_its, width, curves_out + 2 * (size_t)done);
-        if (rc) return rc;
-        const int it = it0 + n - 1;
-        if (M > 0 && (it + 1) % M == 0) {
-            const SaChainsDev g = sc_dev(s, n, n * tries);
-            GGS_HIP(launch_sa_chains_exchange(s->st, g, (SaLoopDev*)s->loop.p, (const SaItDev*)s->sit.p, n - 1, it,
-                                              s->exchange_seed, (it + 1) / M - 1, s->N, (float*)s->curr.p,
-                                              (float*)s->best.p, (unsigned long long*)s->swaps.p));
-            GGS_HIP(hipMemcpyAsync(s->h_loop, s->loop.p, sizeof(SaLoopDev) * s->K, hipMemcpyDeviceToHost, s->st));
-            GGS_HIP(hipMemcpyAsync(s->h_swaps, s->swaps.p, sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost,
-                                   s->st));
-            GGS_HIP(hipStreamSynchronize(s->st));
-        }
-        done += n;
-    }
-    return GGS_OK;
-}
-
-int ggs_sa_chains_state(void* handle, double* best_fit, double* curr_fit, uint64_t* rounds, uint64_t* evaluated,
-                        uint64_t* accepted, uint64_t* swaps_tried, uint64_t* swaps_accepted) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    SaChains* s = (SaChains*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    for (int k = 0; k < s->K; ++k) {    // as of the end of the last ggs_sa_chains_run (or creation)
-        const SaLoopDev& l = s->h_loop[k];
-        if (best_fit) best_fit[k] = l.best_fit;
-        if (curr_fit) curr_fit[k] = l.curr_fit;
-        if (rounds) rounds[k] = l.rounds;
-        if (evaluated) evaluated[k] = l.evaluated;
-        if (accepted) accepted[k] = l.accepted;
-    }
-    if (swaps_tried) *swaps_tried = s->h_swaps[0];
-    if (swaps_accepted) *swaps_accepted = s->h_swaps[1];
-    return GGS_OK;
-}
-
-int ggs_sa_chains_read(void* handle, float* current, float* best) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    SaChains* s = (SaChains*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    const size_t n9 = 9 * (size_t)s->N;
-    GGS_HIP(hipStreamSynchronize(s->st));
-    for (int k = 0; k < s->K && n9; ++k) {
-        if (current)
-            GGS_HIP(hipMemcpy(current + n9 * k, (const float*)s->curr.p + k * s->gstride, sizeof(float) * n9,
-                              hipMemcpyDeviceToHost));
-        if (best)
-            GGS_HIP(hipMemcpy(best + n9 * k, (const float*)s->best.p + k * s->gstride, sizeof(float) * n9,
-                              hipMemcpyDeviceToHost));
-    }
-    return GGS_OK;
-}
-
-void ggs_sa_chains_destroy(void* handle) {
-    if (!handle) return;
-    SaChains* s = (SaChains*)handle;
-    {
-        std::lock_guard<std::mutex> lk(s->c->mu);
-        DeviceGuard dg(s->c->dev);
-        if (s->st) (void)hipStreamSynchronize(s->st);
-        sc_free(s);
-    }
-    delete s;
-}
-
-int ggs_sa_exchange_uniform(uint64_t exchange_seed, int32_t it, int32_t k, double* u) {
-    if (!u || it < 0 || k < 0) return fail(GGS_EINVAL, "bad arguments");
-    *u = sa_exchange_uniform(exchange_seed, (uint32_t)it, (uint32_t)k);
-    return GGS_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// device-resident differential evolution (ggs_de_*; kernels in ggs_ga.hip)
-// ---------------------------------------------------------------------------
-namespace ggs {
-namespace {
-
-// Like a GA session: its own stream, pipeline buffers and finalize counters.
-struct DeSession {
-    DevCtx* c = nullptr;
-    hipStream_t st = nullptr;
-    ggs_ga_config cfg{};
-    ggs_de_params de{};
-    int P = 0, N = 0, cur = 0;     // fits[cur]: the population's fitness
-    DevBuf pop, trials, fits[2], trial_fits, target, mask, best_ind, best_fit, best_row, curves;
-    DevBuf recs, bnds, partials, plan, wpart, order, fctr;
-    int64_t n_curves = 0, curves_cap = 0;
-};
-
-void de_free(DeSession* s) {
-    for (DevBuf* b : {&s->pop, &s->trials, &s->fits[0], &s->fits[1], &s->trial_fits, &s->target, &s->mask,
-                      &s->best_ind, &s->best_fit, &s->best_row, &s->curves, &s->recs, &s->bnds, &s->partials,
-                      &s->plan, &s->wpart, &s->order, &s->fctr})
-        if (b->p) (void)hipFree(b->p);
-    if (s->st) (void)hipStreamDestroy(s->st);
-}
-
-int de_check_params(const ggs_de_params* de) {
-    if (!de) return fail(GGS_EINVAL, "null ggs_de_params");
-    if (de->strategy < 0 || de->strategy > 2)
-        return fail(GGS_EINVAL, "unknown strategy %d (0 rand/1, 1 best/1, 2 current-to-best/1)", de->strategy);
-    if (de->crossover < 0 || de->crossover > 1)
-        return fail(GGS_EINVAL, "unknown crossover %d (0 per gene, 1 per splat)", de->crossover);
-    if (!std::isfinite(de->f_lo) || !std::isfinite(de->f_hi))
-        return fail(GGS_EINVAL, "f_lo and f_hi must be finite");
-    if (de->f_lo > de->f_hi) return fail(GGS_EINVAL, "f_lo=%g must be <= f_hi=%g", de->f_lo, de->f_hi);
-    if (!(de->cr >= 0.0f && de->cr <= 1.0f)) return fail(GGS_EINVAL, "cr=%g must be in [0, 1]", de->cr);
-    return GGS_OK;
-}
-
-DeSelectDev de_select_args(DeSession* s, double* row) {
-    return {(float*)s->pop.p, (const float*)s->trials.p, (const float*)s->fits[s->cur].p,
-            (const float*)s->trial_fits.p, (float*)s->fits[1 - s->cur].p, (int*)s->best_row.p,
-            (double*)s->best_fit.p, (float*)s->best_ind.p, row};
-}
-
-// variation (+ prep), raster (+ finalize), select
-int de_generation(DeSession* s, int gen) {
-    const ggs_ga_config& c = s->cfg;
-    const int P = s->P, N = s->N;
-    const DeParamsDev prm{s->de.strategy, s->de.crossover, s->de.f_lo, s->de.f_hi, s->de.cr, c.scale_log_lo,
-                          c.scale_log_hi};
-    int rc;
-    double* row;
-    if ((rc = curves_row(s->curves, s->n_curves, &s->curves_cap, s->st, &row))) return rc;
-    {
-        ProfScope ps(s->st, 0);
-        GGS_HIP(launch_de_variation(s->st, (const float*)s->pop.p, P, N, prm, c.seed, gen, (const int*)s->best_row.p,
-                                    (float*)s->trials.p, (SplatRec*)s->recs.p, (int4*)s->bnds.p, c.H, c.W,
-                                    c.k_sigma));
-    }
-    if ((rc = raster_fitness(s->st, s->c->simds, (const SplatRec*)s->recs.p, (const int4*)s->bnds.p, P, N, c.H, c.W,
-                             (const float4*)s->plan.p, (float*)s->partials.p, (const float*)s->wpart.p,
-                             c.fitness_mode, (const int*)s->order.p, s->fctr, (float*)s->trial_fits.p, true)))
-        return rc;
-    {
-        ProfScope ps(s->st, 3);
-        GGS_HIP(launch_de_select(s->st, de_select_args(s, row), P, N, 0));
-    }
-    s->cur = 1 - s->cur;
-    s->n_curves += 1;
-    return GGS_OK;
-}
-
-}  // namespace
-}  // namespace ggs
-
-extern "C" {
-
-int ggs_de_create(int32_t device, const ggs_ga_config* cfg, const ggs_de_params* de, const float* target_hw3,
-                  const float* mask_hw, const float* init_pop, void** handle) {
-    if (!cfg || !de || !target_hw3 || !init_pop || !handle) return fail(GGS_EINVAL, "null argument");
-    const ggs_ga_config& c = *cfg;
-    if (c.pop_size < 4 || c.pop_size > ga_breed_max_population())
-        return fail(GGS_EINVAL, "pop_size must be in [4, %d] (three distinct rows besides the target), got %d",
-                    ga_breed_max_population(), c.pop_size);
-    if (c.n_splats < 1) return fail(GGS_EINVAL, "n_splats must be >= 1, got %d", c.n_splats);
-    int rc = check_dims(c.pop_size, c.n_splats, 9, c.H, c.W);
-    if (rc) return rc;
-    if (c.fitness_mode < GGS_FIT_NONE || c.fitness_mode > GGS_FIT_BOOST)
-        return fail(GGS_EINVAL, "bad fitness mode %d", c.fitness_mode);
-    if (c.fitness_mode != GGS_FIT_NONE && !mask_hw) return fail(GGS_EINVAL, "mode needs a mask");
-    if ((rc = de_check_params(de))) return rc;
-    DevCtx* ctx = nullptr;
-    if ((rc = get_ctx(device, &ctx))) return rc;
-    auto s = std::make_unique<DeSession>();
-    s->c = ctx;
-    s->cfg = c;
-    s->de = *de;
-    ga_fill_log_bounds(&s->cfg);
-    s->P = c.pop_size;
-    s->N = c.n_splats;
-    const size_t pb = sizeof(float) * 9 * (size_t)s->P * s->N, hw = (size_t)c.H * c.W;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard dg(ctx->dev);
-    auto bail = [&](int code) { de_free(s.get()); return code; };
-    if (hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess)
-        return bail(fail(GGS_EHIP, "stream creation failed"));
-    int nTX;
-    const size_t slots = 4 * (size_t)raster_tiles(c.H, c.W, &nTX), rows = (size_t)s->P * s->N;
-    if ((rc = ensure(s->pop, pb, s->st)) || (rc = ensure(s->trials, pb, s->st)) ||
-        (rc = ensure(s->fits[0], sizeof(float) * s->P, s->st)) ||
-        (rc = ensure(s->fits[1], sizeof(float) * s->P, s->st)) ||
-        (rc = ensure(s->trial_fits, sizeof(float) * s->P, s->st)) ||
-        (rc = ensure(s->target, sizeof(float) * 3 * hw, s->st)) ||
-        (mask_hw && (rc = ensure(s->mask, sizeof(float) * hw, s->st))) ||
-        (rc = ensure(s->best_ind, sizeof(float) * 9 * s->N, s->st)) ||
-        (rc = ensure(s->best_fit, sizeof(double), s->st)) || (rc = ensure(s->best_row, sizeof(int), s->st)) ||
-        (rc = ensure(s->recs, sizeof(SplatRec) * rows, s->st)) || (rc = ensure(s->bnds, sizeof(int4) * rows, s->st)) ||
-        (rc = ensure(s->partials, sizeof(float) * slots * s->P, s->st)) ||
-        (rc = ensure(s->plan, plan_bytes(c.H, c.W), s->st)) ||
-        (rc = ensure(s->wpart, plan_wsum_bytes(c.H, c.W), s->st)) ||
-        (rc = ensure(s->order, sizeof(int) * (size_t)raster_order_len(c.H, c.W), s->st)))
-        return bail(rc);
-    std::vector<int> order(raster_order_len(c.H, c.W));
-    raster_tile_order(c.H, c.W, order.data());
-    const float* d_mask = mask_hw ? (const float*)s->mask.p : nullptr;
-    if (hipMemcpyAsync(s->target.p, target_hw3, sizeof(float) * 3 * hw, hipMemcpyHostToDevice, s->st) ||
-        (mask_hw && hipMemcpyAsync(s->mask.p, mask_hw, sizeof(float) * hw, hipMemcpyHostToDevice, s->st)) ||
-        hipMemcpyAsync(s->pop.p, init_pop, pb, hipMemcpyHostToDevice, s->st) ||
-        hipMemcpyAsync(s->order.p, order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice, s->st))
-        return bail(fail(GGS_EHIP, "upload failed"));
-    if (launch_plan(s->st, (const float*)s->target.p, d_mask, c.fitness_mode, c.boost_beta, c.H, c.W,
-                    (float4*)s->plan.p, (float*)s->wpart.p) != hipSuccess)
-        return bail(fail(GGS_EHIP, "plan launch failed"));
-    // the initial population through the session's own pipeline
-    {
-        ProfScope ps(s->st, 0);
-        if (launch_prep(s->st, true, (const float*)s->pop.p, (int64_t)rows, 9, c.H, c.W, c.k_sigma,
-                        (SplatRec*)s->recs.p, (int4*)s->bnds.p, nullptr, nullptr, nullptr) != hipSuccess)
-            return bail(fail(GGS_EHIP, "prep launch failed"));
-    }
-    if ((rc = raster_fitness(s->st, ctx->simds, (const SplatRec*)s->recs.p, (const int4*)s->bnds.p, s->P, s->N, c.H,
-                             c.W, (const float4*)s->plan.p, (float*)s->partials.p, (const float*)s->wpart.p,
-                             c.fitness_mode, (const int*)s->order.p, s->fctr, (float*)s->fits[0].p, true)))
-        return bail(rc);
-    double* row;
-    if ((rc = curves_row(s->curves, 0, &s->curves_cap, s->st, &row))) return bail(rc);
-    if (launch_de_select(s->st, de_select_args(s.get(), row), s->P, s->N, 1) != hipSuccess)
-        return bail(fail(GGS_EHIP, "init launch failed"));
-    if (hipStreamSynchronize(s->st) != hipSuccess)     // init_pop / target may be freed on return
-        return bail(fail(GGS_EHIP, "initial evaluation failed"));
-    s->n_curves = 1;
-    *handle = s.release();
-    return GGS_OK;
-}
-
-int ggs_de_set_params(void* handle, const ggs_de_params* de) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    const int rc = de_check_params(de);
-    if (rc) return rc;
-    DeSession* s = (DeSession*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    s->de = *de;                     // a kernel argument of the launches from now on
-    return GGS_OK;
-}
-
-int ggs_de_run(void* handle, int32_t first_gen, int32_t n_gens) {
-    if (!handle || n_gens < 0 || first_gen < 0) return fail(GGS_EINVAL, "bad arguments");
-    DeSession* s = (DeSession*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    for (int g = 0; g < n_gens; ++g) {
-        const int rc = de_generation(s, first_gen + g);
-        if (rc) return rc;
-    }
-    return GGS_OK;
-}
-
-int ggs_de_read(void* handle, float* pop, float* fits, float* trials, float* trial_fits, float* best_ind,
-                double* best_fit, double* curves, int32_t* n_curves) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    DeSession* s = (DeSession*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    GGS_HIP(hipStreamSynchronize(s->st));
-    const size_t pb = sizeof(float) * 9 * (size_t)s->P * s->N;
-    if (pop) GGS_HIP(hipMemcpy(pop, s->pop.p, pb, hipMemcpyDeviceToHost));
-    if (fits) GGS_HIP(hipMemcpy(fits, s->fits[s->cur].p, sizeof(float) * s->P, hipMemcpyDeviceToHost));
-    if (trials) GGS_HIP(hipMemcpy(trials, s->trials.p, pb, hipMemcpyDeviceToHost));
-    if (trial_fits) GGS_HIP(hipMemcpy(trial_fits, s->trial_fits.p, sizeof(float) * s->P, hipMemcpyDeviceToHost));
-    if (best_ind) GGS_HIP(hipMemcpy(best_ind, s->best_ind.p, sizeof(float) * 9 * (size_t)s->N, hipMemcpyDeviceToHost));
-    if (best_fit) GGS_HIP(hipMemcpy(best_fit, s->best_fit.p, sizeof(double), hipMemcpyDeviceToHost));
-    if (curves) GGS_HIP(hipMemcpy(curves, s->curves.p, sizeof(double) * 3 * s->n_curves, hipMemcpyDeviceToHost));
-    if (n_curves) *n_curves = (int32_t)s->n_curves;
-    return GGS_OK;
-}
-
-void ggs_de_destroy(void* handle) {
-    if (!handle) return;
-    DeSession* s = (DeSession*)handle;
-    {
-        std::lock_guard<std::mutex> lk(s->c->mu);
-        DeviceGuard dg(s->c->dev);
-        if (s->st) (void)hipStreamSynchronize(s->st);
-        de_free(s);
-    }
-    delete s;
-}
-
-}  // extern "C"
-
-// ---- Adam refiner (ggs_refine_*) ---------------------------------------------------
-namespace ggs {
-namespace {
-
-// B candidates refined side by side on the session's own stream: per step one
-// gradient call (fitness and gradient of the state x_t), the best-so-far update
-// (x_t, its fitness) and one elementwise Adam update.  The pipeline buffers are the
-// stream's pooled workspace, dropped with the session.
-struct RefineSession {
-    DevCtx* c = nullptr;
-    hipStream_t st = nullptr;
-    ggs_ga_config cfg{};
-    ggs_refine_params prm{};
-    int B = 0, N = 0;
-    int64_t t = 0;                 // Adam steps taken
-    uint64_t plan_key = 0;         // the session's target never changes
-    DevBuf x, m, v, grad, fits, best_x, best_fit, target, mask;
-    // ggs_refine_create_targets: target [K][H][W][3], mask [K][H][W], plan / wpart a plan
-    // set of K made at create; candidate b against image b / group (0: the one target)
-    int K = 1, group = 0;
-    DevBuf plan, wpart;
-    // ggs_refine_create_loss: fits is the image loss of the render against image b / group
-    // (no plan, no mask); the render and its cotangent live in img / cot [B][H][W][3]
-    bool use_loss = false;
-    ggs_loss_params loss{};
-    float bg[3] = {1.f, 1.f, 1.f};
-    DevBuf img, cot;
-};
-
-std::atomic<uint64_t> g_refine_serial{1};
-
-void refine_free(RefineSession* s) {
-    for (DevBuf* b : {&s->x, &s->m, &s->v, &s->grad, &s->fits, &s->best_x, &s->best_fit, &s->target, &s->mask,
-                      &s->plan, &s->wpart, &s->img, &s->cot})
-        if (b->p) (void)hipFree(b->p);
-    if (s->st) {
-        release_workspace(s->c, s->st);
-        (void)hipStreamDestroy(s->st);
-    }
-}
-
-// fitness (and, with grad, the gradient) of the current state into s->fits
-int refine_eval(RefineSession* s, bool grad) {
-    const ggs_ga_config& c = s->cfg;
-    const float* d_mask = s->mask.p ? (const float*)s->mask.p : nullptr;
-    if (s->use_loss) {
-        if (grad)
-            return run_loss_grad(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, GGS_LAYOUT_AXES,
-                                 (const float*)s->target.p, s->group, c.H, c.W, c.k_sigma, s->bg, s->loss,
-                                 (float*)s->fits.p, (float*)s->grad.p, (float*)s->img.p, (float*)s->cot.p);
-        int rc = run_render(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, c.H, c.W, c.k_sigma, s->bg,
-                            (float*)s->img.p, true);
-        if (rc) return rc;
-        return run_image_loss(s->c, s->st, (const float*)s->img.p, s->B, (const float*)s->target.p, s->group, c.H, c.W,
-                              s->loss, (float*)s->fits.p, nullptr);
-    }
-    if (s->group > 0) {
-        if (grad)
-            return run_fitness_grad_planned(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, (const float4*)s->plan.p,
-                                            (const float*)s->wpart.p, (const float*)s->target.p, d_mask,
-                                            c.fitness_mode, c.boost_beta, c.H, c.W, s->group, c.k_sigma,
-                                            (float*)s->fits.p, (float*)s->grad.p);
-        return run_fitness_planned(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, (const float4*)s->plan.p,
-                                   (const float*)s->wpart.p, c.fitness_mode, c.H, c.W, c.k_sigma, (float*)s->fits.p,
-                                   s->group);
-    }
-    if (grad)
-        return run_fitness_grad(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, (const float*)s->target.p, d_mask,
-                                c.fitness_mode, c.boost_beta, c.H, c.W, c.k_sigma, (float*)s->fits.p,
-                                (float*)s->grad.p, s->plan_key);
-    return run_fitness(s->c, s->st, (const float*)s->x.p, s->B, s->N, 9, (const float*)s->target.p, d_mask,
-                       c.fitness_mode, c.boost_beta, c.H, c.W, c.k_sigma, (float*)s->fits.p, s->plan_key);
-}
-
-// ggs_refine_create (group 0: one target and mask), ggs_refine_create_targets
-// (group >= 1: targets [K][H][W][3], masks [K][H][W], one plan set) and
-// ggs_refine_create_loss (loss set: group >= 1, targets [K][H][W][3], no mask and no plan)
-int refine_create(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p, const float* target,
-                  const float* mask, int32_t K, const float* genomes_BN9, int32_t B, int32_t group, void** handle,
-                  const ggs_loss_params* loss = nullptr, const float* bg = nullptr) {
-    if (!cfg || !p || !target || !genomes_BN9 || !handle) return fail(GGS_EINVAL, "null argument");
-    const ggs_ga_config& c = *cfg;
-    int rc = loss ? check_loss_grad(B, c.n_splats, 9, GGS_LAYOUT_AXES, K, group, c.H, c.W, loss)
-             : group == 0 ? check_grad_dims(B, c.n_splats, 9, c.H, c.W, c.fitness_mode, mask)
-                          : check_grad_set(B, c.n_splats, 9, c.H, c.W, c.fitness_mode, mask, K, group);
-    if (rc) return rc;
-    if (!loss && group > 0 && (rc = check_dims(K, 1, 9, c.H, c.W))) return rc;
-    if ((rc = refine_check_params(p))) return rc;
-    DevCtx* ctx = nullptr;
-    if ((rc = get_ctx(device, &ctx))) return rc;
-    auto s = std::make_unique<RefineSession>();
-    s->c = ctx;
-    s->cfg = c;
-    s->prm = *p;
-    ga_fill_log_bounds(&s->cfg);
-    s->B = B;
-    s->N = c.n_splats;
-    s->K = K;
-    s->group = group;
-    if (loss) {
-        s->use_loss = true;
-        s->loss = *loss;
-        if (bg) memcpy(s->bg, bg, sizeof s->bg);
-    }
-    const bool planned = group > 0 && !loss;
-    s->plan_key = (1ull << 63) | g_refine_serial.fetch_add(1);     // host_plan_key never sets bit 63
-    const size_t pb = sizeof(float) * 9 * (size_t)B * s->N, hw = (size_t)K * c.H * c.W;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard dg(ctx->dev);
-    auto bail = [&](int code) { refine_free(s.get()); return code; };
-    if (hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess)
-        return bail(fail(GGS_EHIP, "stream creation failed"));
-    if ((rc = ensure(s->x, pb, s->st)) || (rc = ensure(s->m, pb, s->st)) || (rc = ensure(s->v, pb, s->st)) ||
-        (rc = ensure(s->grad, pb, s->st)) || (rc = ensure(s->best_x, pb, s->st)) ||
-        (rc = ensure(s->fits, sizeof(float) * (size_t)B, s->st)) ||
-        (rc = ensure(s->best_fit, sizeof(double) * (size_t)B, s->st)) ||
-        (rc = ensure(s->target, sizeof(float) * 3 * hw, s->st)) ||
-        (mask && (rc = ensure(s->mask, sizeof(float) * hw, s->st))) ||
-        (planned && ((rc = ensure(s->plan, (size_t)K * plan_bytes(c.H, c.W), s->st)) ||
-                     (rc = ensure(s->wpart, (size_t)K * plan_wsum_bytes(c.H, c.W), s->st)))) ||
-        (loss && ((rc = ensure(s->img, sizeof(float) * 3 * (size_t)B * c.H * c.W, s->st)) ||
-                  (rc = ensure(s->cot, sizeof(float) * 3 * (size_t)B * c.H * c.W, s->st)))))
-        return bail(rc);
-    std::vector<double> inf((size_t)B, (double)INFINITY);
-    if (hipMemcpyAsync(s->target.p, target, sizeof(float) * 3 * hw, hipMemcpyHostToDevice, s->st) ||
-        (mask && hipMemcpyAsync(s->mask.p, mask, sizeof(float) * hw, hipMemcpyHostToDevice, s->st)) ||
-        hipMemcpyAsync(s->x.p, genomes_BN9, pb, hipMemcpyHostToDevice, s->st) ||
-        hipMemcpyAsync(s->best_x.p, genomes_BN9, pb, hipMemcpyHostToDevice, s->st) ||
-        hipMemcpyAsync(s->best_fit.p, inf.data(), sizeof(double) * (size_t)B, hipMemcpyHostToDevice, s->st) ||
-        hipMemsetAsync(s->m.p, 0, pb, s->st) || hipMemsetAsync(s->v.p, 0, pb, s->st) ||
-        hipMemsetAsync(s->grad.p, 0, pb, s->st))
-        return bail(fail(GGS_EHIP, "upload failed"));
-    if (planned &&
-        launch_plan_set(s->st, (const float*)s->target.p, mask ? (const float*)s->mask.p : nullptr, c.fitness_mode,
-                        c.boost_beta, c.H, c.W, K, (float4*)s->plan.p, (float*)s->wpart.p) != hipSuccess)
-        return bail(fail(GGS_EHIP, "plan launch failed"));
-    if (hipStreamSynchronize(s->st) != hipSuccess)     // the caller's arrays may be freed on return
-        return bail(fail(GGS_EHIP, "upload failed"));
-    *handle = s.release();
-    return GGS_OK;
-}
-}  // namespace
-}  // namespace ggs
-extern "C" {
-
-int ggs_refine_create(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p, const float* target_hw3,
-                      const float* mask_hw, const float* genomes_BN9, int32_t B, void** handle) {
-    return ggs::refine_create(device, cfg, p, target_hw3, mask_hw, 1, genomes_BN9, B, 0, handle);
-}
-
-int ggs_refine_create_targets(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p,
-                              const float* targets_khw3, const float* masks_khw, int32_t K, const float* genomes_BN9,
-                              int32_t B, int32_t group, void** handle) {
-    if (group < 1) return fail(GGS_EINVAL, "group=%d must be >= 1", group);
-    return ggs::refine_create(device, cfg, p, targets_khw3, masks_khw, K, genomes_BN9, B, group, handle);
-}
-
-int ggs_refine_create_loss(int32_t device, const ggs_ga_config* cfg, const ggs_refine_params* p,
-                           const ggs_loss_params* loss, const float* bg, const float* targets_khw3, int32_t K,
-                           const float* genomes_BN9, int32_t B, int32_t group, void** handle) {
-    if (!loss) return fail(GGS_EINVAL, "null ggs_loss_params");
-    return ggs::refine_create(device, cfg, p, targets_khw3, nullptr, K, genomes_BN9, B, group, handle, loss, bg);
-}
-
-int ggs_refine_run(void* handle, int32_t n_steps) {
-    if (!handle || n_steps < 0) return fail(GGS_EINVAL, "bad arguments");
-    RefineSession* s = (RefineSession*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    for (int i = 0; i < n_steps; ++i) {
-        int rc;
-        if ((rc = refine_eval(s, true))) return rc;
-        GGS_HIP(launch_refine_best(s->st, (const float*)s->x.p, (const float*)s->fits.p, s->B, s->N,
-                                   (double*)s->best_fit.p, (float*)s->best_x.p));
-        s->t += 1;
-        const RefineStepDev p = refine_step_dev(s->prm, s->cfg, s->t);
-        GGS_HIP(launch_refine_adam(s->st, (float*)s->x.p, (float*)s->m.p, (float*)s->v.p, (const float*)s->grad.p,
-                                   s->B, s->N, p));
-    }
-    return GGS_OK;
-}
-
-int ggs_refine_read(void* handle, float* genomes, float* fits, float* best, float* best_fits, float* last_grad) {
-    if (!handle) return fail(GGS_EINVAL, "null handle");
-    RefineSession* s = (RefineSession*)handle;
-    std::lock_guard<std::mutex> lk(s->c->mu);
-    DeviceGuard dg(s->c->dev);
-    // the current state's own fitness, which may also be the best so far
-    int rc;
-    if ((rc = refine_eval(s, false))) return rc;
-    GGS_HIP(launch_refine_best(s->st, (const float*)s->x.p, (const float*)s->fits.p, s->B, s->N,
-                               (double*)s->best_fit.p, (float*)s->best_x.p));
-    GGS_HIP(hipStreamSynchronize(s->st));
-    const size_t pb = sizeof(float) * 9 * (size_t)s->B * s->N;
-    if (genomes) GGS_HIP(hipMemcpy(genomes, s->x.p, pb, hipMemcpyDeviceToHost));
-    if (fits) GGS_HIP(hipMemcpy(fits, s->fits.p, sizeof(float) * (size_t)s->B, hipMemcpyDeviceToHost));
-    if (best) GGS_HIP(hipMemcpy(best, s->best_x.p, pb, hipMemcpyDeviceToHost));
-    if (best_fits) {
-        std::vector<double> bf((size_t)s->B);
-        GGS_HIP(hipMemcpy(bf.data(), s->best_fit.p, sizeof(double) * (size_t)s->B, hipMemcpyDeviceToHost));
-        for (int b = 0; b < s->B; ++b) best_fits[b] = (float)bf[b];   // float32 fitness values, widened: exact
-    }
-    if (last_grad) GGS_HIP(hipMemcpy(last_grad, s->grad.p, pb, hipMemcpyDeviceToHost));
-    return GGS_OK;
-}
-
-void ggs_refine_destroy(void* handle) {
-    if (!handle) return;
-    RefineSession* s = (RefineSession*)handle;
-    {
-        std::lock_guard<std::mutex> lk(s->c->mu);
-        DeviceGuard dg(s->c->dev);
-        if (s->st) (void)hipStreamSynchronize(s->st);
-        refine_free(s);
-    }
-    delete s;
-}
-
-}  // extern "C"

@@ -589,7 +589,7 @@ int ggs_comm_init_loopback(int32_t device, int32_t n, void** comms) {
 }  // extern "C"
 
 namespace ggs {
-// Single-process fan-out (ggs_capi.cpp): one in-place all-gather per device of
+// Single-process fan-out (the host API in ggs_capi.cpp): one in-place all-gather per device of
 // that device's `per`-float shard of buf[d] (shard d at buf[d] + d*per), grouped
 // so one thread can drive every device.
 int comm_group_allgather_inplace(void* const* comms, int n, hipStream_t const* streams, float* const* bufs,

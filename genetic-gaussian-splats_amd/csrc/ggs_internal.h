@@ -1,4 +1,4 @@
-// Internal declarations shared by ggs_kernels.hip and ggs_capi.cpp.
+// Internal declarations shared by the kernels (*.hip) and the host layer (ggs_host.h, ggs_capi.cpp, ggs_sess_*.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -105,6 +105,7 @@ SIGNATURES = {
     "ggs_profile_enable": (C.c_int, [C.c_int32]),
     "ggs_profile_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "ggs_profile_reset": (None, []),
+    "ggs_workspace_count": (C.c_int, [C.c_int32]),
     "ggs_plan_create": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "ggs_fitness_device_planned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

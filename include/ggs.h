@@ -741,6 +741,12 @@ int ggs_profile_enable(int32_t on);
 int ggs_profile_read(const char* kernel, double* total_ms, int64_t* launches);
 void ggs_profile_reset(void);
 
+/* The number of pooled per-stream pipeline workspaces that device's context holds,
+ * or a negative GGS_E* code.  A session's stream has one while the session lives and
+ * none after its destroy: a leak check that does not depend on free device memory,
+ * which other processes on the same GPU change. */
+int ggs_workspace_count(int32_t device);
+
 #ifdef __cplusplus
 }
 #endif
