@@ -122,7 +122,7 @@ struct DeviceGuard {
 };
 
 // Event pair around one kernel while ggs_profile_enable is on (kernel: 0 prep,
-// 1 raster, 2 finalize, 3 select).
+// 1 raster, 2 finalize, 3 select, 4 one density-control event of a refine session).
 struct ProfScope {
     bool on = false;
     hipEvent_t a = nullptr, b = nullptr;

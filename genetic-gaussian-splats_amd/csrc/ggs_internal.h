@@ -591,6 +591,18 @@ size_t image_loss_partial_bytes(int64_t B, int H, int W);
 hipError_t launch_image_loss(hipStream_t st, const float* img, int64_t B, const float* targets, int group, int H, int W,
                              const float w[3], void* partials, float* loss, float* cot);
 
+// ---- density control of the refiner (ggs_density.hip) --------------------
+// acc [B][N] += the per-pixel norm of grad [B][N][9]'s position columns.
+hipError_t launch_density_acc(hipStream_t st, const float* grad, float* acc, int B, int N, int H, int W);
+// One event on x, m, v [B][N][9]: counts [B][2] zeroed, rank, apply.  M = the
+// effective max_moves (<= N / 2; 0: nothing is launched); dead_list / src_list
+// [B][M], pairs [B][M][2], is_split [B][M], last_n [B]; moves / splits [B] cumulative,
+// may be null.  B <= 65535 (the rank kernel's grid is (ceil(N / 256), B)).
+hipError_t launch_density_event(hipStream_t st, float* x, float* m, float* v, const float* acc, int n_acc, int B, int N,
+                                int H, int W, float log_lo, float log_hi, const ggs_refine_density& d, int M,
+                                int* dead_list, int* src_list, int* counts, int* pairs, int* is_split, int* last_n,
+                                unsigned long long* moves, unsigned long long* splits);
+
 // ---- RCCL (ggs_comm.cpp) ----------------------------------------------------
 // Grouped in-place all-gather over single-process communicators (ggs_comm_init_local):
 // buf[d] holds shard d at buf[d] + d*per; afterwards every buf[d] holds all n shards.

@@ -29,6 +29,56 @@ RefineStepDev refine_step_dev(const ggs_refine_params& prm, const ggs_ga_config&
 
 namespace {
 
+int density_check_params(const ggs_refine_density& d) {
+    if (d.every < 0 || d.start < 0 || d.stop < 0 || d.max_moves < 0)
+        return fail(GGS_EINVAL, "density: every=%d, start=%d, stop=%d, max_moves=%d must be >= 0", d.every, d.start,
+                    d.stop, d.max_moves);
+    if (d.every > 0 && d.max_moves == 0) return fail(GGS_EINVAL, "density: max_moves must be >= 1 when every > 0");
+    const float f[5] = {d.alpha_dead, d.grad_min, d.split_log, d.log_shrink, d.split_offset};
+    for (float x : f)
+        if (!std::isfinite(x)) return fail(GGS_EINVAL, "density: every float parameter must be finite");
+    if (d.alpha_dead < 0.0f || d.alpha_dead > 255.0f)
+        return fail(GGS_EINVAL, "density: alpha_dead=%g must be in [0, 255]", d.alpha_dead);
+    if (d.grad_min < 0.0f) return fail(GGS_EINVAL, "density: grad_min=%g must be >= 0", d.grad_min);
+    if (d.log_shrink < 0.0f) return fail(GGS_EINVAL, "density: log_shrink=%g must be >= 0", d.log_shrink);
+    return GGS_OK;
+}
+
+constexpr int kDensityMaxB = 65535;     // the rank kernel's grid is (ceil(N / 256), B)
+
+// What one event reads and writes beside x, m, v: the accumulator, the two lists, their
+// counters and the event log.
+struct DensityBufs {
+    int M = 0;                     // the effective max_moves, min(max_moves, N / 2)
+    DevBuf acc, dead, src, counts, pairs, is_split, last_n, moves, splits;
+    size_t pair_bytes(int B) const { return sizeof(int) * 2 * (size_t)B * M; }
+
+    // allocated and zeroed on st; `session`: with the accumulator and the cumulative counters
+    int make(int B, int N, int max_moves, bool session, hipStream_t st) {
+        M = std::min(max_moves, N / 2);
+        const size_t lb = std::max<size_t>(sizeof(int) * (size_t)B * M, 4), ib = sizeof(int) * (size_t)B;
+        int rc;
+        if ((rc = ensure(dead, lb, st)) || (rc = ensure(src, lb, st)) || (rc = ensure(counts, 2 * ib, st)) ||
+            (rc = ensure(pairs, 2 * lb, st)) || (rc = ensure(is_split, lb, st)) || (rc = ensure(last_n, ib, st)))
+            return rc;
+        if (session && ((rc = ensure(acc, sizeof(float) * (size_t)B * N, st)) ||
+                        (rc = ensure(moves, 2 * ib, st)) || (rc = ensure(splits, 2 * ib, st))))
+            return rc;
+        // an event with M == 0 launches nothing: the log reads as "no pairs"
+        GGS_HIP(hipMemsetAsync(pairs.p, 0xFF, 2 * lb, st));
+        GGS_HIP(hipMemsetAsync(is_split.p, 0, lb, st));
+        GGS_HIP(hipMemsetAsync(last_n.p, 0, ib, st));
+        GGS_HIP(hipMemsetAsync(dead.p, 0, lb, st));
+        GGS_HIP(hipMemsetAsync(src.p, 0, lb, st));
+        if (session) {
+            GGS_HIP(hipMemsetAsync(acc.p, 0, sizeof(float) * (size_t)B * N, st));
+            GGS_HIP(hipMemsetAsync(moves.p, 0, 2 * ib, st));
+            GGS_HIP(hipMemsetAsync(splits.p, 0, 2 * ib, st));
+        }
+        return GGS_OK;
+    }
+};
+
 // B candidates refined side by side on the session's own stream: per step one
 // gradient call (fitness and gradient of the state x_t), the best-so-far update
 // (x_t, its fitness) and one elementwise Adam update.  The pipeline buffers are the
@@ -48,7 +98,24 @@ struct RefineSession : Session {
     ggs_loss_params loss{};
     float bg[3] = {1.f, 1.f, 1.f};
     DevBuf img, cot;
+    // ggs_refine_set_density: off unless den.every > 0
+    ggs_refine_density den{};
+    DensityBufs db;
+    int n_acc = 0;                 // steps accumulated since the last event
 };
+
+// one relocation event on the session's state, then the accumulator's reset
+int refine_density_event(RefineSession* s) {
+    DensityBufs& d = s->db;
+    ProfScope ps(s->st, 4);
+    GGS_HIP(launch_density_event(s->st, (float*)s->x.p, (float*)s->m.p, (float*)s->v.p, (const float*)d.acc.p, s->n_acc,
+                                 s->B, s->N, s->cfg.H, s->cfg.W, s->cfg.scale_log_lo, s->cfg.scale_log_hi, s->den, d.M,
+                                 (int*)d.dead.p, (int*)d.src.p, (int*)d.counts.p, (int*)d.pairs.p, (int*)d.is_split.p,
+                                 (int*)d.last_n.p, (unsigned long long*)d.moves.p, (unsigned long long*)d.splits.p));
+    GGS_HIP(hipMemsetAsync(d.acc.p, 0, sizeof(float) * (size_t)s->B * s->N, s->st));
+    s->n_acc = 0;
+    return GGS_OK;
+}
 
 // fitness (and, with grad, the gradient) of the current state into s->fits
 int refine_eval(RefineSession* s, bool grad) {
@@ -174,9 +241,119 @@ int ggs_refine_run(void* handle, int32_t n_steps) {
                                    (double*)s->best_fit.p, (float*)s->best_x.p));
         s->t += 1;
         const RefineStepDev p = refine_step_dev(s->prm, s->cfg, s->t);
+        const ggs_refine_density& d = s->den;
+        if (d.every > 0) {
+            GGS_HIP(launch_density_acc(s->st, (const float*)s->grad.p, (float*)s->db.acc.p, s->B, s->N, s->cfg.H,
+                                       s->cfg.W));
+            s->n_acc += 1;
+        }
         GGS_HIP(launch_refine_adam(s->st, (float*)s->x.p, (float*)s->m.p, (float*)s->v.p, (const float*)s->grad.p,
                                    s->B, s->N, p));
+        if (d.every > 0 && s->t % d.every == 0 && s->t >= d.start && (d.stop == 0 || s->t <= d.stop) &&
+            (rc = refine_density_event(s)))
+            return rc;
     }
+    return GGS_OK;
+}
+
+int ggs_refine_set_density(void* handle, const ggs_refine_density* density) {
+    if (!handle) return fail(GGS_EINVAL, "null handle");
+    RefineSession* s = (RefineSession*)handle;
+    int rc;
+    if (density && (rc = density_check_params(*density))) return rc;
+    if (density && density->every > 0 && s->B > kDensityMaxB)
+        return fail(GGS_EINVAL, "density: B=%d candidates exceed the limit %d", s->B, kDensityMaxB);
+    std::lock_guard<std::mutex> lk(s->c->mu);
+    DeviceGuard dg(s->c->dev);
+    if (!density || density->every == 0) {
+        s->den = ggs_refine_density{};
+        return GGS_OK;
+    }
+    DensityBufs nb;                     // the session's own buffers stay until these are ready
+    if ((rc = nb.make(s->B, s->N, density->max_moves, true, s->st))) {
+        (void)hipStreamSynchronize(s->st);
+        return rc;
+    }
+    GGS_HIP(hipStreamSynchronize(s->st));     // steps already queued are done with the old buffers
+    s->db = std::move(nb);
+    s->den = *density;
+    s->n_acc = 0;
+    return GGS_OK;
+}
+
+int ggs_refine_density_read(void* handle, float* acc_BN, int32_t* n_acc, int64_t* moves_B, int64_t* splits_B,
+                            int32_t* last_pairs_B_M_2, int32_t* last_n_B) {
+    if (!handle) return fail(GGS_EINVAL, "null handle");
+    RefineSession* s = (RefineSession*)handle;
+    std::lock_guard<std::mutex> lk(s->c->mu);
+    DeviceGuard dg(s->c->dev);
+    if (s->den.every == 0) return fail(GGS_EINVAL, "density control is off (ggs_refine_set_density)");
+    const DensityBufs& d = s->db;
+    const size_t ib = sizeof(int) * (size_t)s->B;
+    GGS_HIP(hipStreamSynchronize(s->st));
+    if (acc_BN) GGS_HIP(hipMemcpy(acc_BN, d.acc.p, sizeof(float) * (size_t)s->B * s->N, hipMemcpyDeviceToHost));
+    if (n_acc) *n_acc = s->n_acc;
+    if (moves_B) GGS_HIP(hipMemcpy(moves_B, d.moves.p, 2 * ib, hipMemcpyDeviceToHost));
+    if (splits_B) GGS_HIP(hipMemcpy(splits_B, d.splits.p, 2 * ib, hipMemcpyDeviceToHost));
+    if (last_pairs_B_M_2 && d.M > 0)
+        GGS_HIP(hipMemcpy(last_pairs_B_M_2, d.pairs.p, d.pair_bytes(s->B), hipMemcpyDeviceToHost));
+    if (last_n_B) GGS_HIP(hipMemcpy(last_n_B, d.last_n.p, ib, hipMemcpyDeviceToHost));
+    return GGS_OK;
+}
+
+int ggs_density_relocate(int32_t device, const float* x, const float* m, const float* v, const float* acc,
+                         int32_t n_acc, int32_t B, int32_t N, int32_t H, int32_t W, float log_lo, float log_hi,
+                         const ggs_refine_density* params, float* x_out, float* m_out, float* v_out,
+                         int32_t* pairs, int32_t* n_pairs, int32_t* is_split) {
+    if (!params) return fail(GGS_EINVAL, "null ggs_refine_density");
+    int rc = density_check_params(*params);
+    if (rc) return rc;
+    if (B < 1 || N < 1) return fail(GGS_EINVAL, "B=%d and N=%d must be >= 1", B, N);
+    if (B > kDensityMaxB) return fail(GGS_EINVAL, "density: B=%d candidates exceed the limit %d", B, kDensityMaxB);
+    if ((int64_t)B * N * 9 >= (int64_t)1 << 31)
+        return fail(GGS_EINVAL, "B*N*9 = %lld genes exceeds the limit; split the batch", (long long)B * N * 9);
+    if (H < 1 || W < 1) return fail(GGS_EINVAL, "H=%d, W=%d must be >= 1", H, W);
+    if (n_acc < 0) return fail(GGS_EINVAL, "n_acc=%d must be >= 0", n_acc);
+    if (!(log_lo <= log_hi)) return fail(GGS_EINVAL, "log bounds [%g, %g] are not an interval", log_lo, log_hi);
+    const int M = params->every > 0 ? std::min(params->max_moves, N / 2) : 0;
+    if (!x || !m || !v || !acc || !x_out || !m_out || !v_out || !n_pairs || (M > 0 && (!pairs || !is_split)))
+        return fail(GGS_EINVAL, "null array");
+    const size_t pb = sizeof(float) * 9 * (size_t)B * N, ab = sizeof(float) * (size_t)B * N;
+    if (M == 0) {                       // off, or no pair fits: the identity
+        if (x_out != x) memmove(x_out, x, pb);
+        if (m_out != m) memmove(m_out, m, pb);
+        if (v_out != v) memmove(v_out, v, pb);
+        memset(n_pairs, 0, sizeof(int32_t) * (size_t)B);
+        return GGS_OK;
+    }
+    DevCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->dev);
+    const hipStream_t st = c->stream;
+    DevBuf dx, dm, dv, dacc;            // this call's own scratch, freed on return
+    DensityBufs d;
+    struct Sync {                       // ... after the stream has drained, errors included
+        hipStream_t st;
+        ~Sync() { (void)hipStreamSynchronize(st); }
+    } sync{st};
+    if ((rc = ensure(dx, pb, st)) || (rc = ensure(dm, pb, st)) || (rc = ensure(dv, pb, st)) ||
+        (rc = ensure(dacc, ab, st)) || (rc = d.make(B, N, params->max_moves, false, st)))
+        return rc;
+    GGS_HIP(hipMemcpyAsync(dx.p, x, pb, hipMemcpyHostToDevice, st));
+    GGS_HIP(hipMemcpyAsync(dm.p, m, pb, hipMemcpyHostToDevice, st));
+    GGS_HIP(hipMemcpyAsync(dv.p, v, pb, hipMemcpyHostToDevice, st));
+    GGS_HIP(hipMemcpyAsync(dacc.p, acc, ab, hipMemcpyHostToDevice, st));
+    GGS_HIP(launch_density_event(st, (float*)dx.p, (float*)dm.p, (float*)dv.p, (const float*)dacc.p, n_acc, B, N, H, W,
+                                 log_lo, log_hi, *params, d.M, (int*)d.dead.p, (int*)d.src.p, (int*)d.counts.p,
+                                 (int*)d.pairs.p, (int*)d.is_split.p, (int*)d.last_n.p, nullptr, nullptr));
+    GGS_HIP(hipMemcpyAsync(x_out, dx.p, pb, hipMemcpyDeviceToHost, st));
+    GGS_HIP(hipMemcpyAsync(m_out, dm.p, pb, hipMemcpyDeviceToHost, st));
+    GGS_HIP(hipMemcpyAsync(v_out, dv.p, pb, hipMemcpyDeviceToHost, st));
+    GGS_HIP(hipMemcpyAsync(pairs, d.pairs.p, d.pair_bytes(B), hipMemcpyDeviceToHost, st));
+    GGS_HIP(hipMemcpyAsync(is_split, d.is_split.p, sizeof(int) * (size_t)B * d.M, hipMemcpyDeviceToHost, st));
+    GGS_HIP(hipMemcpyAsync(n_pairs, d.last_n.p, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
+    GGS_HIP(hipStreamSynchronize(st));
     return GGS_OK;
 }
 

@@ -69,6 +69,13 @@ class LossParamsC(C.Structure):
     _fields_ = [("w_l1", C.c_float), ("w_mse", C.c_float), ("w_ssim", C.c_float)]
 
 
+class RefineDensity(C.Structure):
+    """ggs_refine_density (include/ggs.h)."""
+    _fields_ = [("every", C.c_int32), ("start", C.c_int32), ("stop", C.c_int32), ("max_moves", C.c_int32),
+                ("alpha_dead", C.c_float), ("grad_min", C.c_float), ("split_log", C.c_float),
+                ("log_shrink", C.c_float), ("split_offset", C.c_float)]
+
+
 class GaPolish(C.Structure):
     """ggs_ga_polish (include/ggs.h)."""
     _fields_ = [("every", C.c_int32), ("n_steps", C.c_int32), ("n_rows", C.c_int32), ("adam", RefineParams)]
@@ -212,6 +219,12 @@ SIGNATURES = {
     "ggs_refine_run": (C.c_int, [C.c_void_p, C.c_int32]),
     "ggs_refine_read": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p]),
     "ggs_refine_destroy": (None, [C.c_void_p]),
+    "ggs_refine_set_density": (C.c_int, [C.c_void_p, C.POINTER(RefineDensity)]),
+    "ggs_refine_density_read": (C.c_int, [C.c_void_p, _f32p, _i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                          _i32p, _i32p]),
+    "ggs_density_relocate": (C.c_int, [C.c_int32, _f32p, _f32p, _f32p, _f32p, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_float, C.c_float, C.POINTER(RefineDensity),
+                                       _f32p, _f32p, _f32p, _i32p, _i32p, _i32p]),
     "ggs_comm_unique_id": (C.c_int, [C.c_void_p]),
     "ggs_comm_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                   C.POINTER(C.c_void_p)]),

@@ -312,6 +312,34 @@ def loss_grad(genomes, targets, H: int, W: int, params=None, *, k_sigma: float =
     return loss, grad
 
 
+def density_relocate(x, m, v, acc, n_acc: int, H: int, W: int, params, log_lo: float, log_hi: float, *,
+                     device=None):
+    """ggs_density_relocate, a stage export: one density-control event by
+    the refine session's own rank and apply kernels on host arrays ``x``, ``m``, ``v``
+    [B,N,9] and ``acc`` [B,N] → ``(x, m, v, pairs, n_pairs, is_split)``, new arrays;
+    ``ggs.refine.relocate`` states the same event in numpy.  One device."""
+    from .refine import density_moves, density_params_c
+    prm = density_params_c(params)
+    xs = [as_f32(a) for a in (x, m, v)]
+    if xs[0].ndim != 3 or xs[0].shape[2] != 9 or any(a.shape != xs[0].shape for a in xs):
+        raise GGSInputError(f"x, m, v must be [B,N,9] alike, got {[tuple(a.shape) for a in xs]}")
+    B, N, _ = xs[0].shape
+    a = as_f32(acc)
+    if a.shape != (B, N):
+        raise GGSInputError(f"acc must be [B,N] = {(B, N)}, got {tuple(a.shape)}")
+    M = density_moves(prm, N)
+    outs = [np.empty_like(b) for b in xs]
+    pairs, is_split = np.full((B, M, 2), -1, np.int32), np.zeros((B, M), np.int32)
+    n_pairs = np.zeros((B,), np.int32)
+    ip = lambda b: b.ctypes.data_as(_i32p)  # noqa: E731
+    # arguments are validated before the library looks for a device
+    check(lib.ggs_density_relocate(device_index(device), _fp(xs[0]), _fp(xs[1]), _fp(xs[2]), _fp(a), int(n_acc), B,
+                                   N, int(H), int(W), float(log_lo), float(log_hi), C.byref(prm), _fp(outs[0]),
+                                   _fp(outs[1]), _fp(outs[2]), ip(pairs), ip(n_pairs), ip(is_split)),
+          "ggs_density_relocate")
+    return outs[0], outs[1], outs[2], pairs, n_pairs, is_split
+
+
 def encode(G_axes) -> np.ndarray:
     """encode.py:62-79 genome_to_renderer_batched (any leading shape, C ≥ 9) → [..., 9]."""
     g = as_f32(G_axes)

@@ -602,6 +602,32 @@ class DeviceRefine:
                                   grad.ctypes.data_as(_f32p)), "ggs_refine_read")
         return {"genomes": x, "fitness": fits, "best": best, "best_fits": bf, "last_grad": grad}
 
+    def set_density(self, params=None) -> None:
+        """Density control (ggs_refine_set_density; ``ggs.DensityParams``) for the steps run
+        after the call, with the accumulator and ``density_stats`` started from zero.  None or
+        ``every = 0``: off, and a session that never had it on keeps its bits."""
+        from .refine import density_moves, density_params_c
+        prm = None if params is None else density_params_c(params)
+        check(lib.ggs_refine_set_density(self.h, None if prm is None else C.byref(prm)), "ggs_refine_set_density")
+        self._moves = 0 if prm is None else density_moves(prm, self.N)
+
+    def density_stats(self) -> Dict[str, np.ndarray]:
+        """ggs_refine_density_read: ``acc`` [B, N] and ``n_acc`` as they stand, ``moves`` /
+        ``splits`` int64 [B] since ``set_density``, and the last event's ``last_pairs`` int32
+        [B, M, 2] ((dead, source) rows, (-1, -1) past ``last_n`` [B]).  Refused while off."""
+        M = getattr(self, "_moves", 0)
+        acc = np.empty((self.B, self.N), np.float32)
+        n_acc = C.c_int32(0)
+        moves, splits = np.empty(self.B, np.int64), np.empty(self.B, np.int64)
+        pairs, last_n = np.full((self.B, M, 2), -1, np.int32), np.empty(self.B, np.int32)
+        i64p = C.POINTER(C.c_int64)
+        check(lib.ggs_refine_density_read(self.h, acc.ctypes.data_as(_f32p), C.byref(n_acc),
+                                          moves.ctypes.data_as(i64p), splits.ctypes.data_as(i64p),
+                                          pairs.ctypes.data_as(_i32p), last_n.ctypes.data_as(_i32p)),
+              "ggs_refine_density_read")
+        return {"acc": acc, "n_acc": int(n_acc.value), "moves": moves, "splits": splits, "last_pairs": pairs,
+                "last_n": last_n}
+
     def close(self) -> None:
         if getattr(self, "h", None):
             lib.ggs_refine_destroy(self.h)

@@ -640,6 +640,69 @@ int ggs_refine_create_loss(int32_t device, const ggs_ga_config* cfg, const ggs_r
                            const ggs_loss_params* loss, const float* bg, const float* targets_khw3, int32_t K,
                            const float* genomes_BN9, int32_t B, int32_t group, void** handle);
 
+/* ---- density control of a refine session: relocation ---------------
+ * The genome keeps its N splats; every `every` steps a candidate's dead splats are
+ * re-used as clones or split halves of its live splats with the largest accumulated
+ * positional gradient.  ggs/refine.py density_accumulate / relocate are the numpy
+ * statement the device is held to bit for bit.  Float32, every operation rounded once
+ * in the written order, division and sqrt correctly rounded.
+ *   accumulate, on every step while on, after the gradient g of x_t and before the Adam
+ *     update: acc[b,s] += sqrt(px px + py py), px = g[b,s,0] / float(max(W - 1, 1)),
+ *     py = g[b,s,1] / float(max(H - 1, 1)); n_acc counts the steps accumulated.
+ *   event, after the Adam update of step t when t % every == 0, t >= start and
+ *     (stop == 0 or t <= stop), per candidate on the updated x:
+ *     dead[s] = x[s,8] < alpha_dead; src[s] = !dead[s] && acc[s] / float(n_acc) > grad_min
+ *     (a NaN is not a source); the dead list ascending by (alpha, index), the source
+ *     list descending by acc, ties to the lower index, -0.0 equal to +0.0;
+ *     n = min(|dead|, |src|, max_moves); pair j < n is (d = dead[j], s = src[j]).
+ *     Clone, when max(x[s,2], x[s,3]) <= split_log: row d becomes row s's nine genes,
+ *     m[d] = v[d] = 0, row s keeps everything.  Split otherwise, from row s's values
+ *     before the event: L = max(x[s,2], x[s,3]), the major axis is a iff
+ *     x[s,2] >= x[s,3]; (ux, uy) = (cos th, sin th) for a, else (-sin th, cos th);
+ *     dlt = split_offset exp(L); dx = (dlt ux) / float(max(W - 1, 1)),
+ *     dy = (dlt uy) / float(max(H - 1, 1)); row s gets x0 = clip(x0 + dx, 0, 1),
+ *     x1 = clip(x1 + dy, 0, 1) and x2, x3 = clip(. - log_shrink, scale_log_lo,
+ *     scale_log_hi), row d the same with - dx, - dy; angle, colour and alpha are copied;
+ *     m and v are zeroed for both rows.  exp, sin and cos are ggs_detmath_eval's.
+ *     Then acc and n_acc are zeroed for every candidate, moved or not.
+ * best, best_fit, last_grad and t are untouched, and the Adam bias corrections stay
+ * global in t.  Genomes that are not finite are not a supported input. */
+typedef struct ggs_refine_density {
+    int32_t every;        /* steps between events; 0 = off */
+    int32_t start;        /* no event before step start */
+    int32_t stop;         /* no event after step stop; 0 = no end */
+    int32_t max_moves;    /* pairs per candidate and event; the effective value is min(max_moves, N / 2) */
+    float alpha_dead;     /* in [0, 255] */
+    float grad_min;       /* >= 0 */
+    float split_log;
+    float log_shrink;     /* >= 0 */
+    float split_offset;
+} ggs_refine_density;
+/* Works on a session of any of the three creates and holds for the steps run after the
+ * call; allocates what it needs and starts acc, n_acc and the event log from zero.
+ * NULL or every == 0: off, and a session that never had it on keeps its bits.
+ * GGS_EINVAL, the session left as it was: negative every, start, stop or max_moves,
+ * max_moves == 0 with every > 0, floats that are not finite, alpha_dead outside
+ * [0, 255], grad_min < 0, log_shrink < 0, more than 65535 candidates. */
+int ggs_refine_set_density(void* handle, const ggs_refine_density* density /* NULL = off */);
+/* Synchronises.  acc_BN [B,N] and *n_acc as they stand; moves_B / splits_B [B]: pairs
+ * moved / of them split since ggs_refine_set_density; last_pairs_B_M_2 [B,M,2]
+ * (M = min(max_moves, N / 2)): the last event's (dead, source) rows, (-1, -1) past
+ * last_n_B[b].  Any pointer may be NULL.  GGS_EINVAL while density control is off. */
+int ggs_refine_density_read(void* handle, float* acc_BN, int32_t* n_acc, int64_t* moves_B, int64_t* splits_B,
+                            int32_t* last_pairs_B_M_2, int32_t* last_n_B);
+/* Stage export (host arrays): one event's rank and apply kernels on x, m, v [B,N,9]
+ * and acc [B,N] -> x_out, m_out, v_out [B,N,9], pairs [B,M,2] ((-1, -1) past
+ * n_pairs[b]), n_pairs [B], is_split [B,M], M = min(max_moves, N / 2).  every == 0:
+ * the identity.  GGS_EINVAL before any device is touched: ggs_refine_set_density's
+ * parameter rules, a NULL params or array (pairs and is_split may be NULL when M is 0),
+ * B or N < 1, B > 65535, B * N * 9 >= 2^31, H or W < 1, n_acc < 0, log_lo > log_hi or
+ * either a NaN. */
+int ggs_density_relocate(int32_t device, const float* x, const float* m, const float* v, const float* acc,
+                         int32_t n_acc, int32_t B, int32_t N, int32_t H, int32_t W, float log_lo, float log_hi,
+                         const ggs_refine_density* params, float* x_out, float* m_out, float* v_out,
+                         int32_t* pairs, int32_t* n_pairs, int32_t* is_split);
+
 /* ---- memetic generations of an island group ----------------------
  * After the survivors of every generation g with g % every == 0 (g counts
  * absolutely, as migrate_every does), and after that generation's migration if
@@ -736,7 +799,8 @@ int ggs_comm_barrier(void* comm);
  * by hipEvents; ggs_profile_read synchronises those events and returns the
  * accumulated milliseconds and launch count for the named kernel (a finalize
  * folded into the raster counts as raster time, no finalize launch).  A DE
- * session's variation counts as "prep" and its select launch as "select". */
+ * session's variation counts as "prep" and its select launch as "select"; one
+ * density-control event of a refine session (rank, apply, accumulator reset) as "density". */
 int ggs_profile_enable(int32_t on);
 int ggs_profile_read(const char* kernel, double* total_ms, int64_t* launches);
 void ggs_profile_reset(void);
