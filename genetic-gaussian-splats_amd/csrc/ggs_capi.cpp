@@ -142,7 +142,7 @@ std::vector<int> g_active;                    // devices the host API fans out o
 bool g_inited = false;
 
 // ---- profiling ----------------------------------------------------------------
-constexpr int kProfKernels = 5;
+constexpr int kProfKernels = 6;
 struct ProfRec {
     int kernel;  // 0 prep, 1 raster, 2 finalize, 3 select (DE)
     hipEvent_t a, b;
@@ -152,7 +152,7 @@ bool g_prof_on = false;
 std::vector<ProfRec> g_prof_pending;
 double g_prof_ms[kProfKernels] = {};
 int64_t g_prof_n[kProfKernels] = {};
-const char* const kKernelNames[kProfKernels] = {"prep", "raster", "finalize", "select", "density"};
+const char* const kKernelNames[kProfKernels] = {"prep", "raster", "finalize", "select", "density", "seed"};
 
 }  // namespace
 
@@ -1579,7 +1579,7 @@ int ggs_profile_read(const char* kernel, double* total_ms, int64_t* launches) {
             return GGS_OK;
         }
     }
-    return fail(GGS_EINVAL, "unknown kernel name '%s' (prep|raster|finalize|select)", kernel ? kernel : "(null)");
+    return fail(GGS_EINVAL, "unknown kernel name '%s' (prep|raster|finalize|select|density|seed)", kernel ? kernel : "(null)");
 }
 
 void ggs_profile_reset(void) {

@@ -74,6 +74,7 @@ struct Workspace {
     DevBuf swords, smasks;            // strip words and masks, prep -> raster (StripWords)
     DevBuf gf9, gi4, gpart, gout;     // fitness gradient: prep's stage outputs, strip partials, unwanted fitness
     DevBuf lpart, limg, lcot;         // image loss: tile partials; ggs_loss_grad's image and cotangent
+    DevBuf seedws;                    // residual-driven placement: launch_seed_sites's scratch
     int order_H = -1, order_W = -1;   // (H, W) the tile order was built for
     bool strips_ok = false;           // ... and whether its strip table holds that canvas
     uint64_t plan_key = 0;            // inputs the plan was built from (0: none / volatile)
@@ -122,7 +123,8 @@ struct DeviceGuard {
 };
 
 // Event pair around one kernel while ggs_profile_enable is on (kernel: 0 prep,
-// 1 raster, 2 finalize, 3 select, 4 one density-control event of a refine session).
+// 1 raster, 2 finalize, 3 select, 4 one density-control event of a refine session,
+// 5 one residual-driven placement).
 struct ProfScope {
     bool on = false;
     hipEvent_t a = nullptr, b = nullptr;

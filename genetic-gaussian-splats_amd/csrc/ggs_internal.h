@@ -603,6 +603,19 @@ hipError_t launch_density_event(hipStream_t st, float* x, float* m, float* v, co
                                 int* dead_list, int* src_list, int* counts, int* pairs, int* is_split, int* last_n,
                                 unsigned long long* moves, unsigned long long* splits);
 
+// ---- residual-driven placement (ggs_seed.hip) ---------------------------
+inline int seed_cells(int H, int W, int cell) { return ((H + cell - 1) / cell) * ((W + cell - 1) / cell); }
+// bytes of launch_seed_sites's scratch (own_err: the error grid is not the caller's)
+size_t seed_scratch_bytes(int B, int H, int W, int cell, int M, bool own_err);
+// One placement: cell, rank (its counters zeroed first) and apply on `st`.  img [B][H][W][3]
+// or null (the constant bg), targets [K][H][W][3], weights [K][H][W] or null, candidate b
+// against image b / group; rows [B][M] or null (prm.first_row + j); x [B][N][9] or null
+// (sites only); err [B][G] or null (kept in the scratch); sites [B][M], n_out [B];
+// M = prm.max_sites.  B <= 65535 (the rank kernel's grid is (ceil(G / 256), B)).
+hipError_t launch_seed_sites(hipStream_t st, const float* img, const float bg[3], const float* targets,
+                             const float* weights, int B, int group, int H, int W, const ggs_seed_params& prm,
+                             const int* rows, float* x, int N, void* scratch, float* err, int* sites, int* n_out);
+
 // ---- RCCL (ggs_comm.cpp) ----------------------------------------------------
 // Grouped in-place all-gather over single-process communicators (ggs_comm_init_local):
 // buf[d] holds shard d at buf[d] + d*per; afterwards every buf[d] holds all n shards.

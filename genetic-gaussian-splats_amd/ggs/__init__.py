@@ -12,8 +12,9 @@ from .api import (LossParams, TargetPlan, TargetPlanSet, as_f32, density_relocat
                   fitness_device,
                   fitness_grad, fitness_grad_device, fitness_population, image_loss, image_loss_device,
                   loss_grad, loss_grad_device, preprocess, profile_enable, profile_read, profile_reset, render,
-                  render_device, render_layout_device, render_vjp, render_vjp_device)
+                  render_device, render_layout_device, render_vjp, render_vjp_device, seed_sites)
 from .de import differential_evolution  # noqa: F401
 from .refine import DensityParams  # noqa: F401
+from .seed import SeedParams, SeedRound, seed_genomes, seed_schedule, seeded_population  # noqa: F401
 
 __version__ = "0.1.0"

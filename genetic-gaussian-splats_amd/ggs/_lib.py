@@ -76,6 +76,17 @@ class RefineDensity(C.Structure):
                 ("log_shrink", C.c_float), ("split_offset", C.c_float)]
 
 
+class SeedParamsC(C.Structure):
+    """ggs_seed_params (include/ggs.h)."""
+    _fields_ = [("cell", C.c_int32), ("max_sites", C.c_int32), ("first_row", C.c_int32), ("err_min", C.c_float),
+                ("log_sigma", C.c_float), ("alpha", C.c_float)]
+
+
+class SeedRoundC(C.Structure):
+    """ggs_seed_round (include/ggs.h)."""
+    _fields_ = [("cell", C.c_int32), ("count", C.c_int32), ("log_sigma", C.c_float), ("alpha", C.c_float)]
+
+
 class GaPolish(C.Structure):
     """ggs_ga_polish (include/ggs.h)."""
     _fields_ = [("every", C.c_int32), ("n_steps", C.c_int32), ("n_rows", C.c_int32), ("adam", RefineParams)]
@@ -225,6 +236,15 @@ SIGNATURES = {
     "ggs_density_relocate": (C.c_int, [C.c_int32, _f32p, _f32p, _f32p, _f32p, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_float, C.c_float, C.POINTER(RefineDensity),
                                        _f32p, _f32p, _f32p, _i32p, _i32p, _i32p]),
+    "ggs_seed_sites_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, _f32p, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SeedParamsC),
+                                        C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ggs_seed_sites": (C.c_int, [C.c_int32, _f32p, _f32p, _f32p, _f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                 C.c_int32, C.POINTER(SeedParamsC), _i32p, _f32p, C.c_int32, _f32p, _i32p, _i32p,
+                                 _f32p]),
+    "ggs_seed_genomes": (C.c_int, [C.c_int32, _f32p, _f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.POINTER(SeedRoundC), C.c_int32, C.c_float, C.c_float, C.c_float, _f32p, _f32p,
+                                   _i32p]),
     "ggs_comm_unique_id": (C.c_int, [C.c_void_p]),
     "ggs_comm_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                   C.POINTER(C.c_void_p)]),

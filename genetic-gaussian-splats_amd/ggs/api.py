@@ -340,6 +340,68 @@ def density_relocate(x, m, v, acc, n_acc: int, H: int, W: int, params, log_lo: f
     return outs[0], outs[1], outs[2], pairs, n_pairs, is_split
 
 
+def seed_sites(genomes, image, targets, params, *, weights=None, group: Optional[int] = None,
+               background=(1.0, 1.0, 1.0), rows=None, device=None):
+    """ggs_seed_sites, a stage export: one residual-driven placement by the
+    cell, rank and apply kernels on host arrays → ``(genomes, sites, n, err)``, new arrays:
+    ``genomes`` [B,N,9] with the sites' rows written (None in, None out: sites only),
+    ``sites`` int32 [B,M], ``n`` int32 [B], ``err`` [B, Gy Gx].  ``image`` [B,H,W,3] or None
+    (the constant ``background``; B is then K ``group``), ``targets`` [K,H,W,3] ([H,W,3]),
+    ``weights`` [K,H,W] or None, ``rows`` int [B,M] or None (``first_row + j``);
+    ``ggs.seed.place_sites`` states the same call in numpy.  One device."""
+    from .seed import seed_params_c
+    prm = seed_params_c(params)
+    tgt = as_f32(targets)
+    if tgt.ndim == 3:
+        tgt = tgt[None]
+    if tgt.ndim != 4 or tgt.shape[3] != 3:
+        raise GGSInputError(f"targets must be [K,H,W,3] or [H,W,3], got {tuple(tgt.shape)}")
+    K, H, W, _ = tgt.shape
+    img = None
+    if image is not None:
+        img = as_f32(image)
+        if img.ndim == 3:
+            img = img[None]
+        if img.ndim != 4 or img.shape[1:] != (H, W, 3):
+            raise GGSInputError(f"image must be [B,H,W,3] with (H, W) = {(H, W)}, got {tuple(img.shape)}")
+    B = img.shape[0] if img is not None else K * (1 if group is None else int(group))
+    if group is None:
+        group = max(B // K, 1)
+    w = None
+    if weights is not None:
+        w = as_f32(weights)
+        if w.ndim == 2:
+            w = w[None]
+        if w.shape != (K, H, W):
+            raise GGSInputError(f"weights must be [K,H,W] = {(K, H, W)}, got {tuple(w.shape)}")
+    x = out = None
+    N = 0
+    if genomes is not None:
+        x = as_f32(genomes)
+        if x.ndim != 3 or x.shape[0] != B or x.shape[2] != 9:
+            raise GGSInputError(f"genomes must be [B,N,9] with B = {B}, got {tuple(x.shape)}")
+        N = x.shape[1]
+        out = np.empty_like(x)
+    M = int(prm.max_sites)
+    r = None
+    if rows is not None:
+        r = np.ascontiguousarray(rows, np.int32)
+        if r.shape != (B, M):
+            raise GGSInputError(f"rows must be [B,M] = {(B, M)}, got {tuple(r.shape)}")
+    c = int(prm.cell)
+    sites = np.full((B, M), -1, np.int32)
+    n = np.zeros((B,), np.int32)
+    err = np.empty((B, -(-H // c) * -(-W // c)), np.float32)
+    bg = _background3(background)
+    ip = lambda b: b.ctypes.data_as(_i32p)  # noqa: E731
+    # arguments are validated before the library looks for a device
+    check(lib.ggs_seed_sites(device_index(device), None if img is None else _fp(img), _fp(bg), _fp(tgt),
+                             None if w is None else _fp(w), B, K, int(group), H, W, C.byref(prm),
+                             None if r is None else ip(r), None if x is None else _fp(x), N,
+                             None if out is None else _fp(out), ip(sites), ip(n), _fp(err)), "ggs_seed_sites")
+    return out, sites, n, err
+
+
 def encode(G_axes) -> np.ndarray:
     """encode.py:62-79 genome_to_renderer_batched (any leading shape, C ≥ 9) → [..., 9]."""
     g = as_f32(G_axes)

@@ -703,6 +703,90 @@ int ggs_density_relocate(int32_t device, const float* x, const float* m, const f
                          const ggs_refine_density* params, float* x_out, float* m_out, float* v_out,
                          int32_t* pairs, int32_t* n_pairs, int32_t* is_split);
 
+/* ---- residual-driven placement: seeding from the target ------------
+ * Where a render misses its target, and the splat to put there.  ggs/seed.py cell_grid /
+ * place_sites are the numpy statement the device is held to bit for bit.  Float32, every
+ * operation rounded once in the written order, division correctly rounded.
+ *   pixel   d = img[b] - targets[b / group] per channel (img NULL: the constant bg);
+ *           e = (dr dr + dg dg) + db db, then e = w e with w = weights[b / group] when
+ *           weights are given.
+ *   cell    the canvas in cells of c x c pixels, Gy = ceil(H / c) by Gx = ceil(W / c),
+ *           cell index gy Gx + gx.  A pixel past the image contributes +0.0 and is not
+ *           counted.  Each of the cell's c pixel columns is summed over y ascending from
+ *           +0.0; the c column sums are reduced by the balanced tree v = v[0::2] + v[1::2]
+ *           repeated (adjacent pairs, then pairs of pairs), which is what a lane
+ *           xor-butterfly with strides 1, 2, 4, ... computes.  err is that sum of e; the
+ *           three target channels are summed in the same order; count is the number of
+ *           in-image pixels; the peak is the cell's pixel of largest e, ties to the
+ *           smaller (y, x).
+ *   sites   a cell is eligible iff err > err_min (a NaN is not); the eligible cells
+ *           descending by err, ties to the lower cell index; the first
+ *           n = min(max_sites, #eligible) are the sites.  A perfect render gives none.
+ *   rows    site j < n writes axes-angle row rows[b][j] (rows NULL: first_row + j):
+ *           x = float(px) / float(max(W - 1, 1)), y = float(py) / float(max(H - 1, 1)),
+ *           log a = log b = log_sigma (the caller clips it to the scale bounds),
+ *           theta = 0, colour c = clip(255 (sum_c / float(count)), 0, 255), alpha = alpha.
+ *           Slots j >= n leave their rows untouched; sites[b][j] is the cell, -1 past n.
+ *           Two slots of one candidate naming the same row is not a supported input.
+ * Images that are not finite are not a supported input.  Deterministic: reruns and other
+ * batches give a candidate the same bits. */
+typedef struct ggs_seed_params {
+    int32_t cell;         /* c: 2, 4, 8, 16, 32 or 64 */
+    int32_t max_sites;    /* M >= 1: sites per candidate */
+    int32_t first_row;    /* first row written when no row list is given; first_row + M <= N */
+    float err_min;        /* >= 0 */
+    float log_sigma;
+    float alpha;          /* in [0, 255] */
+} ggs_seed_params;
+/* One placement on device arrays, enqueued on `stream` with no host synchronisation:
+ * d_img_bhw3 [B,H,W,3] or NULL (bg: host, three floats, NULL = 1, 1, 1), d_targets_khw3
+ * [K,H,W,3], d_weights_khw [K,H,W] or NULL (1), d_rows_BM int32 [B,M] or NULL,
+ * d_genomes_BN9 [B,N,9] updated in place or NULL (sites only; N is then not read),
+ * d_sites_BM int32 [B,M], d_n_B int32 [B], d_err_BG [B, Gy Gx] or NULL.  GGS_EINVAL
+ * before any device is touched: a NULL params, targets, sites or n, a cell size not
+ * listed, max_sites < 1, first_row < 0 or first_row + max_sites > N (with genomes and no
+ * row list), floats that are not finite, err_min < 0, alpha outside [0, 255], the group
+ * rule of ggs_fitness_device_planset (group >= 1, B % group == 0, B / group <= K), B, K,
+ * H or W < 1, N < 1 with genomes, B > 65535, B N 9, B Gy Gx or B max_sites >= 2^31.  A
+ * row of a device row list outside [0, N) is skipped on the device. */
+int ggs_seed_sites_device(int32_t device, void* stream, const float* d_img_bhw3, const float* bg,
+                          const float* d_targets_khw3, const float* d_weights_khw, int32_t B, int32_t K,
+                          int32_t group, int32_t H, int32_t W, const ggs_seed_params* params,
+                          const int32_t* d_rows_BM, float* d_genomes_BN9, int32_t N, int32_t* d_sites_BM,
+                          int32_t* d_n_B, float* d_err_BG);
+/* Stage export (host arrays): one placement on genomes [B,N,9] -> genomes_out [B,N,9]
+ * (both may be NULL together: sites only), sites [B,M], n [B], err [B, Gy Gx] (may be
+ * NULL).  The rules above, and a row of rows_BM outside [0, N) or one of genomes and
+ * genomes_out NULL alone, are GGS_EINVAL before any device is touched; a refused call
+ * leaves its outputs alone. */
+int ggs_seed_sites(int32_t device, const float* img_bhw3, const float* bg, const float* targets_khw3,
+                   const float* weights_khw, int32_t B, int32_t K, int32_t group, int32_t H, int32_t W,
+                   const ggs_seed_params* params, const int32_t* rows_BM, const float* genomes_BN9, int32_t N,
+                   float* genomes_out_BN9, int32_t* sites_BM, int32_t* n_B, float* err_BG);
+/* Greedy coarse-to-fine seeding of K images at once.  Every genome starts as N empty
+ * rows (0.5, 0.5, scale_log_lo, scale_log_lo, 0, 0, 0, 0, 0): alpha 0 blends as the
+ * identity, so N empty rows render exactly the background.  Round r renders the genomes
+ * as they stand (axes layout, k_sigma, bg), finds up to count sites of cell size cell
+ * against image k (err_min) and writes them to the next count rows, the rounds' rows
+ * following one another from row 0; rows a round could not place stay empty.  Coarse
+ * rounds first put the fine splats on top in compositing order.  All rounds are enqueued
+ * on one stream with one synchronisation at the end.  genomes_KN9 [K,N,9]; placed_RK
+ * int32 [n_rounds, K]: the rows each round wrote (may be NULL).  A round with count 0 is
+ * skipped (placed 0).  GGS_EINVAL before any device is touched: NULL targets, rounds
+ * or genomes, n_rounds < 1, a round with a cell size not listed, a negative count, a
+ * log_sigma that is not finite or an alpha outside [0, 255], counts that do not sum to
+ * N, err_min < 0 or not finite, scale_log_lo not finite, K, N, H or W < 1, K > 65535 and
+ * ggs_render's size limits. */
+typedef struct ggs_seed_round {
+    int32_t cell;
+    int32_t count;
+    float log_sigma;
+    float alpha;
+} ggs_seed_round;
+int ggs_seed_genomes(int32_t device, const float* targets_khw3, const float* weights_khw, int32_t K, int32_t H,
+                     int32_t W, int32_t N, const ggs_seed_round* rounds, int32_t n_rounds, float err_min,
+                     float scale_log_lo, float k_sigma, const float* bg, float* genomes_KN9, int32_t* placed_RK);
+
 /* ---- memetic generations of an island group ----------------------
  * After the survivors of every generation g with g % every == 0 (g counts
  * absolutely, as migrate_every does), and after that generation's migration if
@@ -800,7 +884,8 @@ int ggs_comm_barrier(void* comm);
  * accumulated milliseconds and launch count for the named kernel (a finalize
  * folded into the raster counts as raster time, no finalize launch).  A DE
  * session's variation counts as "prep" and its select launch as "select"; one
- * density-control event of a refine session (rank, apply, accumulator reset) as "density". */
+ * density-control event of a refine session (rank, apply, accumulator reset) as "density";
+ * one placement (ggs_seed_*: cell, rank and apply, not the render before it) as "seed". */
 int ggs_profile_enable(int32_t on);
 int ggs_profile_read(const char* kernel, double* total_ms, int64_t* launches);
 void ggs_profile_reset(void);
