@@ -456,7 +456,7 @@ refine_adam_kernel(float* __restrict__ x, float* __restrict__ m, float* __restri
 }
 
 // ---- memetic generations of the island group -------------------------
-constexpr int POLISH_PMAX = 512;    // an island's rows are ranked by the counting rank in LDS (the GA's RANKMAX)
+constexpr int POLISH_PMAX = RANKMAX;    // an island's rows are ranked by the counting rank in LDS, as the GA's
 
 // One workgroup per island: the rows of fitness rank j < R (ascending fitness, ties
 // by lower row: the elite list's rank) become refine candidates k * R + j: x and

@@ -241,7 +241,11 @@ hipError_t launch_finalize(hipStream_t st, const float* partials, const float* w
                            int nTiles, int mode, int H, int W, float* out, const int* live = nullptr,
                            int group = 0);   // group > 0: wpartials of plan set entry b / group
 
-// ---- device GA (ggs_ga.hip) -------------------------------------------------
+// ---- the device searches' size limits (ggs_ga.hip, ggs_sa.hip, ggs_de.hip, ggs_grad.hip) --
+constexpr int SMAX = 4096;     // largest pop_size (ga_max_population): a GA population, an SA session's neighbours
+constexpr int RANKMAX = 512;   // counting ranks below this population size (and the fused breed's limit)
+
+// ---- device GA (ggs_ga.hip; shared draw helpers in ggs_variation.h) -----------
 struct GaParamsDev {            // one generation's operator parameters (float32 as the host path)
     float sig_xy, sig_alog, sig_blog, sig_theta, sig_rgb, sig_alpha;   // build_mut_sigma
     float mutpb, cxpb;
@@ -289,7 +293,7 @@ struct GaBestDev {
     int* updated;
     float* ind;                 // [N*9]
 };
-// ---- device SA loop (ggs_sa_run) ---------------------------------------------
+// ---- device SA loop (ggs_sa_run; kernels in ggs_sa.hip) ------------------------
 // Tries are numbered globally, g = it * tries + k.  A round mutates the next
 // `live` tries from the current state (Philox keyed by (seed, it, k), as
 // ggs_sa_propose), evaluates them, and the accept kernel walks them in order
@@ -371,7 +375,7 @@ hipError_t launch_sa_mutate(hipStream_t st, const SaLoopDev* sl, const SaItDev* 
 // in [0, 1).  Host and device compute the same bits.
 double sa_accept_uniform(uint64_t seed, uint32_t it, uint32_t k);
 
-// ---- SA chain groups (ggs_sa_chains_*) -----------------------------------------
+// ---- SA chain groups (ggs_sa_chains_*; kernels in ggs_sa.hip) -------------------
 // K chains, each the device SA loop above with its own SaLoopDev, Philox seed,
 // temperatures and (optionally) target plan.  Every array gains a leading chain
 // dimension: loop state [K], iteration table [K][n_its], flags [K][n_tries],
@@ -490,7 +494,7 @@ hipError_t launch_ga_migrate_copy(hipStream_t st, int K, float* pop, const float
 hipError_t launch_ga_migrate_install(hipStream_t st, int K, float* fits, int P, int m, int elite_k, const int* mig,
                                      const float* refit, int* elite);
 
-// ---- differential evolution (ggs_de_*; kernels in ggs_ga.hip) -------------------
+// ---- differential evolution (ggs_de_*; kernels in ggs_de.hip) -------------------
 struct DeParamsDev {
     int strategy;               // 0 rand/1, 1 best/1, 2 current-to-best/1
     int crossover;              // 0 per gene, 1 per splat

@@ -1,4 +1,4 @@
-// Device-resident differential evolution (ggs_de_*; kernels in ggs_ga.hip).
+// Device-resident differential evolution (ggs_de_*; kernels in ggs_de.hip).
 // Declared in include/ggs.h.
 #include "ggs_host.h"
 

@@ -17,11 +17,47 @@ struct GaState : Session {
     DevBuf recs, bnds, partials;   // the generation's fused pipeline (with the base's plan, order, fctr)
     int64_t n_curves = 0, curves_cap = 0;
     GaBestDev best() { return {(double*)best_fit.p, (int*)best_src.p, (int*)best_upd.p, (float*)best_ind.p}; }
+
+    // The buffers of K populations of P rows (P, N set) and of a raster batch of B candidates.
+    int alloc(int K, size_t B) {
+        const size_t KP = (size_t)K * P, pb = sizeof(float) * 9 * KP * N;
+        int nTX, rc;
+        const size_t slots = 4 * (size_t)raster_tiles(cfg.H, cfg.W, &nTX);
+        for (DevBuf* b : {&pop[0], &pop[1], &off[0], &off[1]})
+            if ((rc = ensure(*b, std::max<size_t>(pb, 4), st))) return rc;
+        for (DevBuf* b : {&fits[0], &fits[1]})
+            if ((rc = ensure(*b, sizeof(float) * KP, st))) return rc;
+        for (DevBuf* b : {&src, &elite[0], &elite[1]})
+            if ((rc = ensure(*b, sizeof(int) * KP, st))) return rc;
+        if ((rc = ensure(off_fits, sizeof(float) * std::max<size_t>(B, 1), st)) ||
+            (rc = ensure(best_ind, std::max<size_t>(sizeof(float) * 9 * (size_t)K * N, 4), st)) ||
+            (rc = ensure(best_fit, sizeof(double) * K, st)) || (rc = ensure(best_src, sizeof(int) * K, st)) ||
+            (rc = ensure(best_upd, sizeof(int) * K, st)) ||
+            (rc = ensure(recs, sizeof(SplatRec) * std::max<size_t>(B * N, 1), st)) ||
+            (rc = ensure(bnds, sizeof(int4) * std::max<size_t>(B * N, 1), st)) ||
+            (rc = ensure(partials, sizeof(float) * slots * std::max<size_t>(B, 1), st)))
+            return rc;
+        return GGS_OK;
+    }
+    // The fused breed's view of the pending generation: it closes into the other
+    // buffers, its statistics into `row` of the curves.
+    BreedDev breed(double* row) {
+        const int nxt = 1 - cur;
+        return {(const float*)pop[cur].p, (const float*)fits[cur].p, (const float*)off[ocur].p,
+                (const float*)off_fits.p, (const int*)elite[cur].p, (int*)elite[nxt].p, (float*)pop[nxt].p,
+                (float*)fits[nxt].p, row, best(), cfg.elite_k};
+    }
+    // The pending generation's survivors and gather are enqueued (on their own or
+    // inside a breed): the other buffers are current and the curves have its row.
+    void closed() {
+        cur = 1 - cur;
+        n_curves += 1;
+        pending = false;
+    }
 };
 
 struct GaSession : GaState {
     using GaState::GaState;
-    int nTiles = 0;
     DevBuf draws;
     void* comm = nullptr;          // ggs_ga_set_comm: offspring fitness sharded over ranks
     int nranks = 1, rank = 0;
@@ -139,9 +175,7 @@ int ga_flush(GaSession* s) {
                                 FitReduce{}, (int*)s->elite[nxt].p));
     GGS_HIP(launch_ga_gather(s->st, (const float*)s->pop[s->cur].p, (const float*)s->off[s->ocur].p, P, N,
                              (const int*)s->src.p, (float*)s->pop[nxt].p, s->best(), 0));
-    s->cur = nxt;
-    s->n_curves += 1;
-    s->pending = false;
+    s->closed();
     return GGS_OK;
 }
 
@@ -165,21 +199,16 @@ int ga_generation(GaSession* s, int gen, int total, const ggs_ga_draws* hd) {
     const int per = (Pe + s->nranks - 1) / s->nranks;
     const int b0 = std::min(Pe, s->rank * per), nb = std::min(Pe, b0 + per) - b0;
     if (s->pending && breed_fused() && P <= ga_breed_max_population()) {   // fused up to this population
-        const int nxt = 1 - s->cur;
         double* row;
         if ((rc = ga_curves_row(s, 1, &row))) return rc;
-        BreedDev br{(const float*)s->pop[s->cur].p, (const float*)s->fits[s->cur].p,
-                    (const float*)s->off[s->ocur].p, (const float*)s->off_fits.p,
-                    (const int*)s->elite[s->cur].p, (int*)s->elite[nxt].p, (float*)s->pop[nxt].p,
-                    (float*)s->fits[nxt].p, row, s->best(), c.elite_k};
+        const BreedDev br = s->breed(row);
         {
             ProfScope ps(s->st, 0);
             GGS_HIP(launch_ga_variation(s->st, nullptr, nullptr, P, N, prm, d, c.seed, gen, (float*)s->off[onew].p,
                                         P, (SplatRec*)s->recs.p, (int4*)s->bnds.p, c.H, c.W, c.k_sigma, nullptr,
                                         nullptr, &br));
         }
-        s->cur = nxt;
-        s->n_curves += 1;
+        s->closed();
     } else {
         if ((rc = ga_flush(s))) return rc;
         ProfScope ps(s->st, 0);
@@ -245,23 +274,7 @@ int ggs_ga_create(int32_t device, const ggs_ga_config* cfg, const float* target_
     DeviceGuard dg(ctx->dev);
     auto bail = [&](int code) { return fail_session(s, code); };
     if ((rc = s->open(target_hw3, mask_hw, 1, 1, true))) return bail(rc);
-    for (DevBuf* b : {&s->pop[0], &s->pop[1], &s->off[0], &s->off[1]})
-        if ((rc = ensure(*b, std::max<size_t>(pb, 4), s->st))) return bail(rc);
-    for (DevBuf* b : {&s->fits[0], &s->fits[1], &s->off_fits})
-        if ((rc = ensure(*b, sizeof(float) * s->P, s->st))) return bail(rc);
-    for (DevBuf* b : {&s->src, &s->elite[0], &s->elite[1]})
-        if ((rc = ensure(*b, sizeof(int) * s->P, s->st))) return bail(rc);
-    if ((rc = ensure(s->best_ind, std::max<size_t>(sizeof(float) * 9 * s->N, 4), s->st))) return bail(rc);
-    if ((rc = ensure(s->best_fit, sizeof(double), s->st))) return bail(rc);
-    if ((rc = ensure(s->best_src, sizeof(int), s->st))) return bail(rc);
-    if ((rc = ensure(s->best_upd, sizeof(int), s->st))) return bail(rc);
-    int nTX;
-    s->nTiles = raster_tiles(c.H, c.W, &nTX);
-    const size_t slots = 4 * (size_t)s->nTiles;
-    if ((rc = ensure(s->recs, sizeof(SplatRec) * std::max<size_t>((size_t)s->P * s->N, 1), s->st)) ||
-        (rc = ensure(s->bnds, sizeof(int4) * std::max<size_t>((size_t)s->P * s->N, 1), s->st)) ||
-        (rc = ensure(s->partials, sizeof(float) * slots * s->P, s->st)))
-        return bail(rc);
+    if ((rc = s->alloc(1, (size_t)s->P))) return bail(rc);     // all P offspring get records
     if (hipMemcpyAsync(s->pop[0].p, init_pop, pb, hipMemcpyHostToDevice, s->st))
         return bail(fail(GGS_EHIP, "upload failed"));
     if ((rc = run_fitness(ctx, s->st, (const float*)s->pop[0].p, s->P, s->N, 9, (const float*)s->target.p,
@@ -447,9 +460,7 @@ int gi_flush(GaIslands* s) {
     GGS_HIP(launch_ga_gather_islands(s->st, s->K, (const float*)s->pop[s->cur].p, (const float*)s->off[s->ocur].p,
                                      s->P, s->N, s->cfg.elite_k, (const int*)s->src.p, (float*)s->pop[nxt].p,
                                      s->best(), 0));
-    s->cur = nxt;
-    s->n_curves += 1;
-    s->pending = false;
+    s->closed();
     if (gi_migrates(s, s->pending_gen) && !s->multi)
         GGS_HIP(launch_ga_migrate(s->st, s->K, (float*)s->pop[nxt].p, (float*)s->fits[nxt].p, s->P, s->N,
                                   s->n_migrants, s->cfg.elite_k, (int*)s->mig.p, (int*)s->elite[nxt].p));
@@ -489,21 +500,16 @@ int gi_generation(GaIslands* s, int gen, int total) {
     // a generation whose survivors are followed by a migration or a polish is closed
     // unfused (flush, migrate, polish); the plain variation launch then breeds from pop / fits
     if (s->pending && breed_fused() && !gi_migrates(s, s->pending_gen) && !gi_polishes(s, s->pending_gen)) {
-        const int nxt = 1 - s->cur;
         double* row;
         if ((rc = ga_curves_row(s, s->K, &row))) return rc;
-        BreedDev br{(const float*)s->pop[s->cur].p, (const float*)s->fits[s->cur].p,
-                    (const float*)s->off[s->ocur].p, (const float*)s->off_fits.p,
-                    (const int*)s->elite[s->cur].p, (int*)s->elite[nxt].p, (float*)s->pop[nxt].p,
-                    (float*)s->fits[nxt].p, row, s->best(), c.elite_k};
+        const BreedDev br = s->breed(row);
         {
             ProfScope ps(s->st, 0);
             GGS_HIP(launch_ga_variation_islands(s->st, K, nullptr, nullptr, P, N, prm, (const uint64_t*)s->seeds.p,
                                                 gen, (float*)s->off[onew].p, (SplatRec*)s->recs.p,
                                                 (int4*)s->bnds.p, c.H, c.W, c.k_sigma, c.elite_k, &br));
         }
-        s->cur = nxt;
-        s->n_curves += 1;
+        s->closed();
     } else {
         if ((rc = gi_flush(s))) return rc;
         ProfScope ps(s->st, 0);
@@ -569,29 +575,13 @@ int gi_create(int32_t device, const ggs_ga_config* cfg, const ggs_ga_islands* is
     DeviceGuard dg(ctx->dev);
     auto bail = [&](int code) { return fail_session(s, code); };
     if ((rc = s->open(target_hw3, mask_hw, nplans, nplans, true))) return bail(rc);
-    for (DevBuf* b : {&s->pop[0], &s->pop[1], &s->off[0], &s->off[1]})
-        if ((rc = ensure(*b, std::max<size_t>(pb, 4), s->st))) return bail(rc);
-    for (DevBuf* b : {&s->fits[0], &s->fits[1]})
-        if ((rc = ensure(*b, sizeof(float) * KP, s->st))) return bail(rc);
-    if ((rc = ensure(s->off_fits, sizeof(float) * std::max<size_t>(B, 1), s->st))) return bail(rc);
-    for (DevBuf* b : {&s->src, &s->elite[0], &s->elite[1]})
-        if ((rc = ensure(*b, sizeof(int) * KP, s->st))) return bail(rc);
+    if ((rc = s->alloc(K, B))) return bail(rc);
     // migration scratch: row lists, zeroed so that an entry is a valid row whatever the fitness values
     if ((rc = ensure_zeroed(s->mig, sizeof(int) * 2 * (size_t)std::max(s->n_migrants, 1) * K, s->st)))
         return bail(rc);
-    if ((rc = ensure(s->best_ind, std::max<size_t>(sizeof(float) * 9 * (size_t)K * N, 4), s->st))) return bail(rc);
-    if ((rc = ensure(s->best_fit, sizeof(double) * K, s->st))) return bail(rc);
-    if ((rc = ensure(s->best_src, sizeof(int) * K, s->st))) return bail(rc);
-    if ((rc = ensure(s->best_upd, sizeof(int) * K, s->st))) return bail(rc);
     if ((rc = ensure(s->seeds, sizeof(uint64_t) * K, s->st))) return bail(rc);
     if (Bm && ((rc = ensure(s->mig_gen, std::max<size_t>(sizeof(float) * 9 * Bm * N, 4), s->st)) ||
                (rc = ensure(s->mig_fits, sizeof(float) * Bm, s->st))))
-        return bail(rc);
-    int nTX;
-    const size_t slots = 4 * (size_t)raster_tiles(c.H, c.W, &nTX);
-    if ((rc = ensure(s->recs, sizeof(SplatRec) * std::max<size_t>(B * N, 1), s->st)) ||
-        (rc = ensure(s->bnds, sizeof(int4) * std::max<size_t>(B * N, 1), s->st)) ||
-        (rc = ensure(s->partials, sizeof(float) * slots * std::max<size_t>(B, 1), s->st)))
         return bail(rc);
     if (hipMemcpyAsync(s->pop[0].p, init_pops, pb, hipMemcpyHostToDevice, s->st) ||
         hipMemcpyAsync(s->seeds.p, isl->seeds, sizeof(uint64_t) * K, hipMemcpyHostToDevice, s->st))

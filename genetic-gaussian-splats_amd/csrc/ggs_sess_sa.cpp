@@ -1,5 +1,5 @@
 // Device-resident simulated annealing: lone sessions (ggs_sa_*) and chain groups
-// (ggs_sa_chains_*); kernels in ggs_ga.hip.  Declared in include/ggs.h.
+// (ggs_sa_chains_*); kernels in ggs_sa.hip.  Declared in include/ggs.h.
 #include "ggs_host.h"
 
 namespace ggs {
@@ -50,6 +50,171 @@ int sa_eval(SaSession* s, const float* G, int n, SplatRec* recs, int4* bnds, flo
                           (const float*)s->wpart.p, c.fitness_mode, (const int*)s->order.p, s->fctr, fits, false,
                           dirty ? (const unsigned char*)s->dirty.p : nullptr, (const float*)s->cur_part.p);
 }
+
+// ---- the round driver of ggs_sa_run and ggs_sa_chains_run ---------------------------
+int sa_check_run(int first_it, int n_its, int tries, const double* temps, int width, int cap,
+                 const double* curves_out) {
+    if (first_it < 0 || n_its < 0 || tries < 1) return fail(GGS_EINVAL, "need first_it >= 0, n_its >= 0, tries >= 1");
+    if (n_its > 0 && (!temps || !curves_out)) return fail(GGS_EINVAL, "null temps / curves");
+    if (width < 0 || width > cap) return fail(GGS_EINVAL, "width=%d outside [0, %d]", width, cap);
+    if ((int64_t)(first_it + (int64_t)n_its) * tries > INT32_MAX)
+        return fail(GGS_EINVAL, "iterations x tries must stay below 2^31");
+    return GGS_OK;
+}
+
+int64_t sa_rounds(int64_t remaining, int32_t est, int64_t cap) {   // ceil(remaining / est) in [1, cap]
+    const int64_t e = std::max<int64_t>(1, est);
+    return std::min<int64_t>(cap, std::max<int64_t>(1, (std::max<int64_t>(remaining, 0) + e - 1) / e));
+}
+// Diagnostic override of the bound (tools/probe/sa_pmc_r03b.sh reproduces the
+// round-2 crash with it lifted); not part of the C ABI.
+int64_t sa_rounds_per_sync(int64_t remaining, int32_t est) {
+    static const int64_t cap = [] {
+        const char* v = getenv("GGS_SA_MAX_ROUNDS_PER_SYNC");
+        return v ? std::max<int64_t>(1, atoll(v)) : (int64_t)GGS_SA_MAX_ROUNDS_PER_SYNC;
+    }();
+    return sa_rounds(remaining, est, cap);
+}
+
+// Adaptive width (sa_width_rule): a round's fixed cost in neighbour evaluations,
+// half the number of candidates whose strip waves fit in the GPU's raster wave
+// slots (CUs x 4 SIMDs x 3 waves): small canvases add neighbours almost for free
+// until the chip fills.  2048^2 (2,048 strips): 0.75 — measured at configs[4],
+// start of a run, a round of 1 neighbour costs 191 us and of 2 297 us (r = 0.81);
+// 512^2 (128 strips): 12
+double sa_width_r(int nTiles) {
+    static const double wave_slots = [] {
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) == hipSuccess)
+            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        return 12.0 * (double)cus;
+    }();
+    return std::max(0.25, 0.5 * wave_slots / (double)(4 * nTiles));
+}
+
+struct SaChunk {                // what the driver hands a session's launches
+    const SaItDev* sit;         // [K][n] the iteration table (device)
+    int64_t pos0, end;          // the chunk's tries, the same for every chain
+    double width_r;
+    GaParamsDev prm;            // mutate-only; sigmas replaced per neighbour from sit
+    SaRoundDev rd;              // what every session sets; gcap is the driver's
+};
+
+// One chunk of iterations [first_it, first_it + n) over the K loop states of session
+// s (SaSession: K = 1; SaChains), temps[k * tstride + i] and curves_out[(k * tstride
+// + i) * 2 + {0, 1}].  The session supplies its launches: begin(x, bw), the chunk's
+// start and flags (bw: the first round's width); round(x, gcap), one round in grids
+// of gcap neighbours per chain; finish(), its read-backs ahead of the final sync.
+// est_with_width: after a sync the lone loop sizes a batch by the remaining tries
+// over the pending round's live count, the group over max(batch width, live).  The
+// sync cadence and the `rounds` / `evaluated` counters follow, so each keeps its own.
+template <class S, class Begin, class Round, class Finish>
+int sa_drive(S* s, int K, int first_it, int n, int total_iters, int tries, const double* temps, int tstride,
+             int width, double* curves_out, bool est_with_width, Begin begin, Round round, Finish finish) {
+    const ggs_ga_config& c = s->cfg;
+    std::vector<SaItDev> tab((size_t)K * n);
+    for (int i = 0; i < n; ++i) {
+        const GaParamsDev q = ga_params(c, first_it + i, total_iters);
+        for (int k = 0; k < K; ++k)
+            tab[(size_t)k * n + i] = SaItDev{{q.sig_xy, q.sig_alog, q.sig_blog, q.sig_theta, q.sig_rgb, q.sig_alpha},
+                                             {0.f, 0.f}, temps[(size_t)k * tstride + i]};
+    }
+    SaChunk x{};
+    x.pos0 = (int64_t)first_it * tries;
+    x.end = x.pos0 + (int64_t)n * tries;
+    const int64_t end = x.end;
+    int rc;
+    if ((rc = ensure(s->sit, sizeof(SaItDev) * tab.size(), s->st)) ||
+        (rc = ensure(s->curves, sizeof(double) * 2 * tab.size(), s->st)) ||
+        (rc = ensure(s->flags, sizeof(int) * (size_t)(end - x.pos0) * K, s->st)))
+        return rc;
+    x.sit = (const SaItDev*)s->sit.p;
+    GGS_HIP(hipMemcpyAsync(s->sit.p, tab.data(), sizeof(SaItDev) * tab.size(), hipMemcpyHostToDevice, s->st));
+    x.width_r = sa_width_r(s->nTiles);
+    // Width of a batch of rounds: the rule's width at the acceptance rates of the
+    // last sync, used by every round of the batch and the size of their mutation
+    // and raster grids — not the session capacity with the width chosen per round
+    // on the device: unused neighbour slots are not free (a lone 2048^2 neighbour in
+    // a 16-slot grid ran 216 us per round instead of 191: the early-exit strip waves
+    // of the other slots stream through the free wave slots beside it).  The
+    // unfinished chains share a round, so its fixed cost is divided among them, at
+    // their mean acceptance rate.  The pending round (computed by the
+    // previous batch) keeps its width.
+    SaLoopDev* h = s->h_loop();
+    bool fresh = true;              // before the chunk's first sync: every chain is unfinished
+    auto unfinished = [&](int k) { return fresh || h[k].pos < end; };
+    auto batch_width = [&]() {
+        if (width > 0) return std::min(s->cap, width);
+        double p = 0.0;
+        int u = 0;
+        for (int k = 0; k < K; ++k)
+            if (unfinished(k)) { p += h[k].acc_rate; ++u; }
+        u = std::max(u, 1);
+        return std::min(s->cap, std::max(1, sa_width_rule(p / u, s->cap, x.width_r / u)));
+    };
+    int bw = batch_width(), gcap = bw;
+    x.prm = ga_params(c, first_it, total_iters);
+    x.prm.mutate_only = 1;
+    x.prm.o_base = 0;
+    x.rd.partials = (const float*)s->nb_part.p;
+    x.rd.wpartials = (const float*)s->wpart.p;
+    x.rd.nslots = 4 * s->nTiles;
+    x.rd.mode = c.fitness_mode;
+    x.rd.N = s->N;
+    x.rd.hw = (double)c.H * (double)c.W;
+    x.rd.fits_out = (float*)s->nb_fits.p;
+    x.rd.mutpb = c.mutpb;
+    x.rd.curves = (double*)s->curves.p;
+    x.rd.curr = (float*)s->curr.p;
+    x.rd.best = (float*)s->best.p;
+    x.rd.nb = (const float*)s->nb.p;
+    if ((rc = begin(x, bw))) return rc;
+    // Rounds are enqueued in batches with one host sync between batches: a round
+    // consumes at most its width of a chain's tries, so ceil(longest remaining /
+    // width) rounds never overshoot the chunk (rounds past its end would be empty
+    // launches anyway).  A batch holds at most GGS_SA_MAX_ROUNDS_PER_SYNC rounds
+    // (ggs_sa_rounds_per_sync): unbounded, a 256-iteration chunk at high acceptance
+    // queued ~1,000 rounds = 4,000 dispatches behind one sync, and rocprofv3's PMC
+    // dispatch interception crashed the host thread inside the launch call
+    // (docs/EXPERIMENTS.md §9).
+    int64_t remaining = end - x.pos0;
+    int est = gcap;
+    for (;;) {
+        int64_t R = sa_rounds_per_sync(remaining, est);
+        // the batch width comes from the acceptance rates at this sync: while a
+        // rate has little history (a session's first tries) sync every 2 rounds
+        uint64_t ev = UINT64_MAX;
+        for (int k = 0; k < K; ++k)
+            if (unfinished(k)) ev = std::min<uint64_t>(ev, h[k].evaluated);
+        if (ev < 64) R = std::min<int64_t>(R, 2);
+        x.rd.gcap = bw;
+        for (int64_t r = 0; r < R; ++r) {
+            if ((rc = round(x, gcap))) return rc;
+            gcap = bw;                  // after the pending round: every round has width bw
+        }
+        GGS_HIP(hipMemcpyAsync(h, s->loop.p, sizeof(SaLoopDev) * K, hipMemcpyDeviceToHost, s->st));
+        GGS_HIP(hipStreamSynchronize(s->st));
+        fresh = false;
+        remaining = 0;
+        int live = 1;
+        for (int k = 0; k < K; ++k) {
+            remaining = std::max<int64_t>(remaining, end - h[k].pos);
+            live = std::max(live, (int)h[k].live);
+        }
+        if (remaining <= 0) break;
+        bw = batch_width();
+        gcap = std::max(bw, live);      // the grids also hold the pending round
+        est = est_with_width ? gcap : live;
+    }
+    std::vector<double> hc(2 * tab.size());
+    GGS_HIP(hipMemcpyAsync(hc.data(), s->curves.p, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, s->st));
+    if ((rc = finish())) return rc;
+    GGS_HIP(hipStreamSynchronize(s->st));
+    for (int k = 0; k < K; ++k)
+        memcpy(curves_out + 2 * (size_t)k * tstride, hc.data() + 2 * (size_t)k * n, sizeof(double) * 2 * (size_t)n);
+    return GGS_OK;
+}
+
 
 }  // namespace
 }  // namespace ggs
@@ -179,32 +344,15 @@ int ggs_sa_commit(void* handle, int32_t j, int32_t update_best) {
 }
 
 int64_t ggs_sa_rounds_per_sync(int64_t remaining, int32_t est) {
-    const int64_t e = std::max<int64_t>(1, est);
-    const int64_t R = std::max<int64_t>(1, (std::max<int64_t>(remaining, 0) + e - 1) / e);
-    return std::min<int64_t>(R, GGS_SA_MAX_ROUNDS_PER_SYNC);
-}
-
-// Diagnostic override of the bound (tools/probe/sa_pmc_r03b.sh reproduces the
-// round-2 crash with it lifted); not part of the C ABI.
-static int64_t sa_rounds_per_sync(int64_t remaining, int32_t est) {
-    static const int64_t cap = [] {
-        const char* v = getenv("GGS_SA_MAX_ROUNDS_PER_SYNC");
-        return v ? std::max<int64_t>(1, atoll(v)) : (int64_t)0;
-    }();
-    if (!cap) return ggs_sa_rounds_per_sync(remaining, est);
-    const int64_t e = std::max<int64_t>(1, est);
-    return std::min<int64_t>(cap, std::max<int64_t>(1, (std::max<int64_t>(remaining, 0) + e - 1) / e));
+    return sa_rounds(remaining, est, GGS_SA_MAX_ROUNDS_PER_SYNC);
 }
 
 int ggs_sa_run(void* handle, int32_t first_it, int32_t n_its, int32_t total_iters, int32_t tries,
                const double* temps, int32_t width, double* curves_out) {
     if (!handle) return fail(GGS_EINVAL, "null handle");
     SaSession* s = (SaSession*)handle;
-    if (first_it < 0 || n_its < 0 || tries < 1) return fail(GGS_EINVAL, "need first_it >= 0, n_its >= 0, tries >= 1");
-    if (n_its > 0 && (!temps || !curves_out)) return fail(GGS_EINVAL, "null temps / curves");
-    if (width < 0 || width > s->cap) return fail(GGS_EINVAL, "width=%d outside [0, %d]", width, s->cap);
-    if ((int64_t)(first_it + (int64_t)n_its) * tries > INT32_MAX)
-        return fail(GGS_EINVAL, "iterations x tries must stay below 2^31");
+    int rc = sa_check_run(first_it, n_its, tries, temps, width, s->cap, curves_out);
+    if (rc) return rc;
     if (s->driver == 1) return fail(GGS_EINVAL, "this SA session is driven by ggs_sa_propose/commit");
     if (n_its == 0) return GGS_OK;
     std::lock_guard<std::mutex> lk(s->c->mu);
@@ -212,79 +360,21 @@ int ggs_sa_run(void* handle, int32_t first_it, int32_t n_its, int32_t total_iter
     s->driver = 2;
     if (!s->incremental) s->cur_cache_valid = false;
     const ggs_ga_config& c = s->cfg;
-    std::vector<SaItDev> tab((size_t)n_its);
-    for (int i = 0; i < n_its; ++i) {
-        const GaParamsDev q = ga_params(c, first_it + i, total_iters);
-        tab[i] = SaItDev{{q.sig_xy, q.sig_alog, q.sig_blog, q.sig_theta, q.sig_rgb, q.sig_alpha}, {0.f, 0.f},
-                         temps[i]};
-    }
-    int rc;
-    if ((rc = ensure(s->sit, sizeof(SaItDev) * (size_t)n_its, s->st)) ||
-        (rc = ensure(s->curves, sizeof(double) * 2 * (size_t)n_its, s->st)))
-        return rc;
     SaLoopDev* loop = (SaLoopDev*)s->loop.p;
-    const SaItDev* sit = (const SaItDev*)s->sit.p;
-    double* curves = (double*)s->curves.p;
-    GGS_HIP(hipMemcpyAsync(s->sit.p, tab.data(), sizeof(SaItDev) * (size_t)n_its, hipMemcpyHostToDevice, s->st));
-    const int64_t pos0 = (int64_t)first_it * tries, end = pos0 + (int64_t)n_its * tries;
-    // adaptive width (sa_width_rule): a round's fixed cost in neighbour evaluations,
-    // half the number of candidates whose strip waves fit in the GPU's raster wave
-    // slots (CUs x 4 SIMDs x 3 waves): small canvases add neighbours almost for free
-    // until the chip fills.  2048^2 (2,048 strips): 0.75 — measured at configs[4],
-    // start of a run, a round of 1 neighbour costs 191 us and of 2 297 us (r = 0.81);
-    // 512^2 (128 strips): 12
-    static const double wave_slots = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess)
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        return 12.0 * (double)cus;
-    }();
-    const double width_r = std::max(0.25, 0.5 * wave_slots / (double)(4 * s->nTiles));
-    // Width of a batch of rounds: the rule's width at the acceptance rate of the
-    // last sync, used by every round of the batch and the size of their mutation
-    // and raster grids — not the session capacity with the width chosen per round
-    // on the device: unused neighbour slots are not free (a lone 2048^2 neighbour in
-    // a 16-slot grid ran 216 us per round instead of 191: the early-exit strip waves
-    // of the other slots stream through the free wave slots beside it).  The
-    // pending round (computed by the previous batch) keeps its width; the
-    // trajectory does not depend on the width.
-    auto batch_width = [&]() {
-        const int w = width > 0 ? width : sa_width_rule(s->h_loop()->acc_rate, s->cap, width_r);
-        return std::min(s->cap, std::max(w, 1));
-    };
-    int bw = batch_width(), gcap = bw;
-    GGS_HIP(launch_sa_begin(s->st, loop, pos0, end, tries, first_it, s->cap, width, width_r, bw));
-    if ((rc = ensure(s->flags, sizeof(int) * (size_t)(end - pos0), s->st))) return rc;
-    GGS_HIP(launch_sa_flags(s->st, pos0, (int)(end - pos0), tries, c.seed, c.mutpb, s->N, (int*)s->flags.p));
-    GaParamsDev prm = ga_params(c, first_it, total_iters);   // sigmas replaced per neighbour from sit
-    prm.mutate_only = 1;
-    prm.o_base = 0;
-    const int nslots = 4 * s->nTiles;
     const float bg[3] = {1.f, 1.f, 1.f};
     const int* live = &loop->live;
-    SaRoundDev rd{};
-    rd.partials = (const float*)s->nb_part.p;
-    rd.wpartials = (const float*)s->wpart.p;
-    rd.nslots = nslots;
-    rd.mode = c.fitness_mode;
-    rd.N = s->N;
-    rd.hw = (double)c.H * (double)c.W;
-    rd.fits_out = (float*)s->nb_fits.p;
-    rd.seed = c.seed;
-    rd.mutpb = c.mutpb;
-    rd.curves = curves;
-    rd.curr = (float*)s->curr.p;
-    rd.best = (float*)s->best.p;
-    rd.nb = (const float*)s->nb.p;
-    rd.cur_recs = s->incremental ? (SplatRec*)s->cur_recs.p : nullptr;
-    rd.nb_recs = (const SplatRec*)s->nb_recs.p;
-    rd.cur_part = (float*)s->cur_part.p;
+    const uint64_t evaluated0 = s->h_loop()->evaluated;
+    auto begin = [&](const SaChunk& x, int bw) -> int {
+        GGS_HIP(launch_sa_begin(s->st, loop, x.pos0, x.end, tries, first_it, s->cap, width, x.width_r, bw));
+        GGS_HIP(launch_sa_flags(s->st, x.pos0, (int)(x.end - x.pos0), tries, c.seed, c.mutpb, s->N, (int*)s->flags.p));
+        return GGS_OK;
+    };
     // one round: mutate (+ records) and swap, [dirty strips], raster, then one
     // workgroup for fitness, acceptance, install and the next round's flags
-    auto round = [&]() -> int {
+    auto round = [&](const SaChunk& x, int gcap) -> int {
         {
             ProfScope ps(s->st, 0);
-            GGS_HIP(launch_sa_mutate(s->st, loop, sit, prm, c.seed, s->N, gcap, (int*)s->flags.p,
+            GGS_HIP(launch_sa_mutate(s->st, loop, x.sit, x.prm, c.seed, s->N, gcap, (int*)s->flags.p,
                                      (const float*)s->curr.p, (float*)s->nb.p, (float*)s->sizes.p,
                                      (SplatRec*)s->nb_recs.p, (int4*)s->nb_bnds.p, c.H, c.W, c.k_sigma));
         }
@@ -300,43 +390,24 @@ int ggs_sa_run(void* handle, int32_t first_it, int32_t n_its, int32_t total_iter
                                   s->incremental ? (const unsigned char*)s->dirty.p : nullptr,
                                   (const float*)s->cur_part.p, live, nullptr, s->c->simds));
         }
-        rd.gcap = bw;
-        GGS_HIP(launch_sa_accept(s->st, loop, sit, rd));
+        SaRoundDev rd = x.rd;       // + the one chain's seed and the incremental path's state
+        rd.seed = c.seed;
+        rd.cur_recs = s->incremental ? (SplatRec*)s->cur_recs.p : nullptr;
+        rd.nb_recs = (const SplatRec*)s->nb_recs.p;
+        rd.cur_part = (float*)s->cur_part.p;
+        GGS_HIP(launch_sa_accept(s->st, loop, x.sit, rd));
         return GGS_OK;
     };
-    // Rounds are enqueued in batches with one host sync between batches: a round
-    // consumes at most its width in tries, so ceil(remaining / width) rounds never
-    // overshoot the chunk (rounds past its end would be empty launches anyway).
-    // A batch holds at most GGS_SA_MAX_ROUNDS_PER_SYNC rounds (ggs_sa_rounds_per_sync):
-    // unbounded, a 256-iteration chunk at high acceptance queued ~1,000 rounds =
-    // 4,000 dispatches behind one sync, and rocprofv3's PMC dispatch interception
-    // crashed the host thread inside the launch call (docs/EXPERIMENTS.md §9).
-    const uint64_t evaluated0 = s->h_loop()->evaluated;
-    int64_t remaining = end - pos0;
-    int est = gcap;
-    for (;;) {
-        int64_t R = sa_rounds_per_sync(remaining, est);
-        // the batch width comes from the acceptance rate at this sync: while the
-        // rate has little history (a session's first tries) sync every 2 rounds
-        if (s->h_loop()->evaluated < 64) R = std::min<int64_t>(R, 2);
-        for (int64_t r = 0; r < R; ++r) {
-            if ((rc = round())) return rc;
-            gcap = bw;                  // after the pending round: every round has width bw
+    auto finish = [&]() -> int {
+        if (s->incremental) {
+            GGS_HIP(hipMemcpyAsync(s->h_counters(), s->counters.p, sizeof(unsigned), hipMemcpyDeviceToHost, s->st));
+            GGS_HIP(hipMemsetAsync(s->counters.p, 0, sizeof(unsigned), s->st));
         }
-        GGS_HIP(hipMemcpyAsync(s->h_loop(), loop, sizeof(SaLoopDev), hipMemcpyDeviceToHost, s->st));
-        GGS_HIP(hipStreamSynchronize(s->st));
-        if (s->h_loop()->pos >= end) break;
-        remaining = end - s->h_loop()->pos;
-        bw = batch_width();
-        gcap = std::max(bw, (int)s->h_loop()->live);     // the grids also hold the pending round
-        est = std::max(1, (int)s->h_loop()->live);
-    }
-    GGS_HIP(hipMemcpyAsync(curves_out, curves, sizeof(double) * 2 * (size_t)n_its, hipMemcpyDeviceToHost, s->st));
-    if (s->incremental) {
-        GGS_HIP(hipMemcpyAsync(s->h_counters(), s->counters.p, sizeof(unsigned), hipMemcpyDeviceToHost, s->st));
-        GGS_HIP(hipMemsetAsync(s->counters.p, 0, sizeof(unsigned), s->st));
-    }
-    GGS_HIP(hipStreamSynchronize(s->st));
+        return GGS_OK;
+    };
+    if ((rc = sa_drive(s, 1, first_it, n_its, total_iters, tries, temps, n_its, width, curves_out, false, begin, round,
+                       finish)))
+        return rc;
     if (s->incremental) s->n_changed += s->h_counters()[0];
     s->n_proposed += s->h_loop()->evaluated - evaluated0;
     return GGS_OK;
@@ -538,74 +609,21 @@ int sc_create(int32_t device, const ggs_ga_config* cfg, const ggs_sa_chains* ch,
 int sc_run_chunk(SaChains* s, int first_it, int n, int total_iters, int tries, const double* temps, int tstride,
                  int width, double* curves_out) {
     const ggs_ga_config& c = s->cfg;
-    const int K = s->K;
-    std::vector<SaItDev> tab((size_t)K * n);
-    for (int i = 0; i < n; ++i) {
-        const GaParamsDev q = ga_params(c, first_it + i, total_iters);
-        for (int k = 0; k < K; ++k)
-            tab[(size_t)k * n + i] = SaItDev{{q.sig_xy, q.sig_alog, q.sig_blog, q.sig_theta, q.sig_rgb, q.sig_alpha},
-                                             {0.f, 0.f}, temps[(size_t)k * tstride + i]};
-    }
-    const int64_t pos0 = (int64_t)first_it * tries, end = pos0 + (int64_t)n * tries;
-    const int n_tries = (int)(end - pos0);
-    int rc;
-    if ((rc = ensure(s->sit, sizeof(SaItDev) * tab.size(), s->st)) ||
-        (rc = ensure(s->curves, sizeof(double) * 2 * tab.size(), s->st)) ||
-        (rc = ensure(s->flags, sizeof(int) * (size_t)n_tries * K, s->st)))
-        return rc;
-    const SaChainsDev g = sc_dev(s, n, n_tries);
+    const SaChainsDev g = sc_dev(s, n, n * tries);
     SaLoopDev* loop = (SaLoopDev*)s->loop.p;
-    const SaItDev* sit = (const SaItDev*)s->sit.p;
-    GGS_HIP(hipMemcpyAsync(s->sit.p, tab.data(), sizeof(SaItDev) * tab.size(), hipMemcpyHostToDevice, s->st));
-    // Adaptive width for the group: the lone session's rule with the
-    // round's fixed cost (ggs_sa_run's width_r, in neighbour evaluations) divided
-    // by the number of unfinished chains, which share that round, at the mean
-    // acceptance rate of those chains.  One width per batch for all chains.
-    static const double wave_slots = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess)
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        return 12.0 * (double)cus;
-    }();
-    const double width_r = std::max(0.25, 0.5 * wave_slots / (double)(4 * s->nTiles));
-    bool fresh = true;              // before the chunk's first sync: every chain is unfinished
-    auto unfinished = [&](int k) { return fresh || s->h_loop()[k].pos < end; };
-    auto batch_width = [&]() {
-        if (width > 0) return std::min(s->cap, width);
-        double p = 0.0;
-        int u = 0;
-        for (int k = 0; k < K; ++k)
-            if (unfinished(k)) { p += s->h_loop()[k].acc_rate; ++u; }
-        u = std::max(u, 1);
-        return std::min(s->cap, std::max(1, sa_width_rule(p / u, s->cap, width_r / u)));
-    };
-    int bw = batch_width(), gcap = bw;
-    GGS_HIP(launch_sa_chains_begin(s->st, g, loop, pos0, end, tries, first_it, width, width_r, bw));
-    GGS_HIP(launch_sa_chains_flags(s->st, g, pos0, tries, c.mutpb, s->N, (int*)s->flags.p));
-    GaParamsDev prm = ga_params(c, first_it, total_iters);   // sigmas replaced per neighbour from sit
-    prm.mutate_only = 1;
-    prm.o_base = 0;
     const float bg[3] = {1.f, 1.f, 1.f};
-    SaRoundDev rd{};
-    rd.partials = (const float*)s->nb_part.p;
-    rd.wpartials = (const float*)s->wpart.p;
-    rd.nslots = 4 * s->nTiles;
-    rd.mode = c.fitness_mode;
-    rd.N = s->N;
-    rd.hw = (double)c.H * (double)c.W;
-    rd.fits_out = (float*)s->nb_fits.p;
-    rd.mutpb = c.mutpb;
-    rd.curves = (double*)s->curves.p;
-    rd.curr = (float*)s->curr.p;
-    rd.best = (float*)s->best.p;
-    rd.nb = (const float*)s->nb.p;
+    auto begin = [&](const SaChunk& x, int bw) -> int {
+        GGS_HIP(launch_sa_chains_begin(s->st, g, loop, x.pos0, x.end, tries, first_it, width, x.width_r, bw));
+        GGS_HIP(launch_sa_chains_flags(s->st, g, x.pos0, tries, c.mutpb, s->N, (int*)s->flags.p));
+        return GGS_OK;
+    };
     // one round: mutate + swap over the listed neighbours, one raster launch over
     // exactly that many candidates, the chains' accept workgroups, the next list
-    auto round = [&]() -> int {
-        const int B = K * gcap;
+    auto round = [&](const SaChunk& x, int gcap) -> int {
+        const int B = s->K * gcap;
         {
             ProfScope ps(s->st, 0);
-            GGS_HIP(launch_sa_chains_mutate(s->st, g, loop, sit, prm, s->N, B, (const int*)s->flags.p,
+            GGS_HIP(launch_sa_chains_mutate(s->st, g, loop, x.sit, x.prm, s->N, B, (const int*)s->flags.p,
                                             (const float*)s->curr.p, (float*)s->nb.p, (float*)s->sizes.p,
                                             (SplatRec*)s->nb_recs.p, (int4*)s->nb_bnds.p, c.H, c.W, c.k_sigma));
         }
@@ -620,45 +638,11 @@ int sc_run_chunk(SaChains* s, int first_it, int n, int total_iters, int tries, c
                                       c.W, bg, nullptr, (const float4*)s->plan.p, (float*)s->nb_part.p,
                                       (const int*)s->order.p, nullptr, nullptr, g.total, nullptr, s->c->simds));
         }
-        rd.gcap = bw;
-        GGS_HIP(launch_sa_chains_accept(s->st, g, loop, sit, rd));
+        GGS_HIP(launch_sa_chains_accept(s->st, g, loop, x.sit, x.rd));
         return GGS_OK;
     };
-    // Batches of rounds with one host sync between them, as ggs_sa_run: the batch
-    // ends when every chain's pos >= end, a round consumes at most its width of a
-    // chain's tries, so ceil(longest remaining / width) rounds never overshoot.
-    int64_t remaining = end - pos0;
-    int est = gcap;
-    for (;;) {
-        int64_t R = sa_rounds_per_sync(remaining, est);
-        uint64_t ev = UINT64_MAX;
-        for (int k = 0; k < K; ++k)
-            if (unfinished(k)) ev = std::min<uint64_t>(ev, s->h_loop()[k].evaluated);
-        if (ev < 64) R = std::min<int64_t>(R, 2);      // little acceptance history yet
-        for (int64_t r = 0; r < R; ++r) {
-            if ((rc = round())) return rc;
-            gcap = bw;                  // after the pending round: every round has width bw
-        }
-        GGS_HIP(hipMemcpyAsync(s->h_loop(), loop, sizeof(SaLoopDev) * K, hipMemcpyDeviceToHost, s->st));
-        GGS_HIP(hipStreamSynchronize(s->st));
-        fresh = false;
-        remaining = 0;
-        int live = 1;
-        for (int k = 0; k < K; ++k) {
-            remaining = std::max<int64_t>(remaining, end - s->h_loop()[k].pos);
-            live = std::max(live, (int)s->h_loop()[k].live);
-        }
-        if (remaining <= 0) break;
-        bw = batch_width();
-        gcap = std::max(bw, live);      // the grids also hold the pending round
-        est = gcap;
-    }
-    std::vector<double> h(2 * tab.size());
-    GGS_HIP(hipMemcpyAsync(h.data(), s->curves.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s->st));
-    GGS_HIP(hipStreamSynchronize(s->st));
-    for (int k = 0; k < K; ++k)
-        memcpy(curves_out + 2 * (size_t)k * tstride, h.data() + 2 * (size_t)k * n, sizeof(double) * 2 * (size_t)n);
-    return GGS_OK;
+    return sa_drive(s, s->K, first_it, n, total_iters, tries, temps, tstride, width, curves_out, true, begin, round,
+                    [] { return (int)GGS_OK; });
 }
 
 }  // namespace
@@ -682,11 +666,7 @@ int ggs_sa_chains_run(void* handle, int32_t first_it, int32_t n_its, int32_t tot
                       const double* temps, int32_t width, double* curves_out) {
     if (!handle) return fail(GGS_EINVAL, "null handle");
     SaChains* s = (SaChains*)handle;
-    if (first_it < 0 || n_its < 0 || tries < 1) return fail(GGS_EINVAL, "need first_it >= 0, n_its >= 0, tries >= 1");
-    if (n_its > 0 && (!temps || !curves_out)) return fail(GGS_EINVAL, "null temps / curves");
-    if (width < 0 || width > s->cap) return fail(GGS_EINVAL, "width=%d outside [0, %d]", width, s->cap);
-    if ((int64_t)(first_it + (int64_t)n_its) * tries > INT32_MAX)
-        return fail(GGS_EINVAL, "iterations x tries must stay below 2^31");
+    if (int rc = sa_check_run(first_it, n_its, tries, temps, width, s->cap, curves_out)) return rc;
     if (n_its == 0) return GGS_OK;
     std::lock_guard<std::mutex> lk(s->c->mu);
     DeviceGuard dg(s->c->dev);

@@ -10,7 +10,7 @@ ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 TMP=$(mktemp -d /tmp/ggs_rev.XXXXXX)
 mkdir -p "$TMP/pkg/csrc" "$TMP/include"
 if [ "$REV" = WORK ]; then
-  cp "$ROOT"/genetic-gaussian-splats_amd/csrc/{Makefile,*.hip,*.cpp,*.h} "$TMP/pkg/csrc/"
+  cp "$ROOT"/genetic-gaussian-splats_amd/csrc/{Makefile,*.hip,*.cpp,*.h,*.inc} "$TMP/pkg/csrc/"
   cp "$ROOT"/include/*.h "$TMP/include/"
 else
   git -C "$ROOT" archive "$REV" genetic-gaussian-splats_amd/csrc include | tar -x -C "$TMP"
